@@ -8,7 +8,14 @@ the packed statistics across ranks, and the statistics' copy to the host
 (what the M-step consumes).  Inputs are synthetic and
 resident in HBM before the timed region.
 
-Single GPU:   python bench.py [--steps K --warmup W --config C4]
+A plain run sets up, settles the clocks, warms up, times the K steps and prints
+the result line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also
+writes what the last timed step computed (stats, L_elbo, hat_Z as DIR/*.npy).
+--full adds everything else after the timed steps: synchronous pacing, per-kernel
+breakdown and roofline, the dense schedule, the EM iteration, host math, the
+shard simulation, the CPU baseline and the parity sample against the oracle.
+
+Single GPU:   python bench.py [--steps K --warmup W --config C4] [--full]
 Multi GPU:    python bench.py --gpus N   (starts N rank processes itself), or
               python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 Rank 0 prints one JSON line.
@@ -192,6 +199,31 @@ def cpu_baseline(vo, base_np, consts, T, N_total, K, target_s):
                 seconds=t, n_sample=n, multi=multi), pr, n
 
 
+DUMP_BYTES_PER_ARRAY = 20 << 20   # three arrays: under 64 MB in all
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_BYTES_PER_ARRAY):
+    """Write each tensor of `arrays` as dirname/<name>.npy (float64).  One larger than
+    max_bytes is cut to a fixed sample of its rows (seeded, ascending, the same for
+    every run of the same shape).  Returns {name: [shape written, shape computed]}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        full = list(t.shape)
+        row_bytes = 8 * max(1, t[0].numel()) if t.dim() > 1 else 8
+        if t.shape[0] * row_bytes > max_bytes:
+            keep = np.sort(np.random.default_rng(20240607).choice(
+                t.shape[0], size=max(1, max_bytes // row_bytes), replace=False))
+            t = t.index_select(0, torch.as_tensor(keep, device=t.device))
+        a = t.detach().cpu().numpy().astype(np.float64, copy=False)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        shapes[name] = [list(a.shape), full]
+    return shapes
+
+
 def rank_launch_command(n, argv, port):
     """The torch.distributed.run command that starts n rank processes of this script
     with the same arguments (one process per GPU, rendezvous on 127.0.0.1)."""
@@ -248,6 +280,17 @@ def main():
     ap.add_argument("--config", default="C4")
     ap.add_argument("--N", type=int, default=None, help="override the number of base HMMs")
     ap.add_argument("--tau", type=int, default=None, help="override tau (experiments only)")
+    ap.add_argument("--settle-ms", type=float, default=600.0,
+                    help="untimed E-steps, run-ahead as in the timed region, for at least this "
+                         "long before the warmup steps: the GPU's clocks settle (0: none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the packed "
+                         "statistics, L_elbo, hat_Z) as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check "
+                         "(synchronous pacing, per-kernel breakdown and roofline, dense schedule, "
+                         "EM iteration, host math, shard simulation, CPU baseline, parity sample); "
+                         "the options below this one only act with --full")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-sample", action="store_true")
@@ -256,9 +299,6 @@ def main():
                     help="EM iterations timed for the em_iteration block (0: skip)")
     ap.add_argument("--no-shard-sim", action="store_true",
                     help="skip the single-GPU run at the 8-GPU shard size (N/8 bases)")
-    ap.add_argument("--settle-ms", type=float, default=600.0,
-                    help="untimed E-steps, run-ahead as in the timed region, for at least this "
-                         "long before the warmup steps: the GPU's clocks settle (0: none)")
     args = ap.parse_args()
     try:
         mode, world = resolve_world(args.gpus, os.environ)
@@ -452,7 +492,9 @@ def main():
     # launch stream around the roofline's kernel) and only in every TIME_EVERY-th
     # E-step: an event record is a queue marker that costs ~5 us of idle GPU on
     # each side of the kernel (10 us of a 160 us C3 step).  The per-kernel
-    # breakdown comes from a separate instrumented pass below.
+    # breakdown comes from a separate instrumented pass below (--full).  A plain run
+    # keeps these events too, though only --full reports them: `value` is the rate
+    # of the same timed region with and without --full.
     time_every = 1 if args.steps < 8 else 4
     # E-steps as the C++ EM loop issues them (vbhem_em_run): step k + 1 is enqueued
     # before the host waits for step k's statistics (one step of run-ahead), so the
@@ -481,6 +523,66 @@ def main():
         per_rank_s = [float(g.item()) for g in gath]
     dt = max(per_rank_s)
     tk = _capi.timing_read()
+
+    def finish():
+        if rccl is not None:
+            rccl.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    # the result line of a plain run; --full adds the secondary blocks below
+    res = {
+        "metric": METRIC,
+        "value": args.steps / dt,
+        "unit": "E-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle": dict(settle, note="untimed run-ahead E-steps before the warmup steps, "
+                                    "until the clocks settle (--settle-ms)"),
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "full": args.full,
+        "data": "synthetic (BASELINE.md generator, seeded), resident in HBM",
+        "config": {"workload": (f"{args.config}: N={N} base HMMs, K={K} clusters, S={S} states, "
+                                f"Sb={Sb}, d={d}, {'full' if cov == 1 else 'diag'} cov, tau={T}, "
+                                f"Nv={opt['Nv']}"),
+                   "N": N, "K": K, "S": S, "Sb": Sb, "d": d, "tau": T,
+                   "parallelism": f"bases sharded over {world} GPU(s), 1 RCCL all-reduce/E-step"},
+        "collective": dict(
+            ({"kind": ("native RCCL communicator (vbhem_rccl_allreduce_to: all-reduce, then "
+                       "an in-stream kernel copy into the pinned statistics buffer)"
+                       if hs_dev is not None else
+                       "native RCCL communicator (vbhem_rccl_allreduce_sum, then a stream copy)"),
+              "ranks": world}
+             if rccl is not None else
+             {"kind": ("torch.distributed all_reduce (%s backend)" % backend
+                       if world > 1 else "none (one rank)"),
+              "ranks": world, "rccl_error": rccl_err}),
+            statistics_doubles=int(stats.numel()),
+            shard_bases_per_rank=[shard_range(N, r, world)[1] - shard_range(N, r, world)[0]
+                                  for r in range(world)],
+            ms_per_step_per_rank=[s / args.steps * 1e3 for s in per_rank_s]),
+        "pacing": ("one E-step of run-ahead (the C++ EM loop's): step k+1 is enqueued before "
+                   "the host waits for step k's statistics in pinned memory"
+                   + (" -- by polling the completion word the step's last kernel writes "
+                      "(vbhem_arm_done_word)" if word is not None else " -- by an event")),
+        "pairs_per_s": N * K * args.steps / dt,
+    }
+    # what the last timed step left for its caller: the packed statistics in pinned host
+    # memory (all-reduced over the ranks), L_elbo and hat_Z of this rank's bases
+    if args.dump_outputs and rank == 0:
+        res["outputs"] = dump_outputs(args.dump_outputs,
+                                      {"stats": stats, "L_elbo": eng.LL, "hat_Z": eng.hatZ})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res))
+        finish()
+        return
+
     # the same steps with the host waiting on each before launching the next (the
     # rate of an E-step whose statistics must be on the host before anything else)
     torch.cuda.synchronize()
@@ -699,10 +801,7 @@ def main():
         del eng_s
 
     if rank != 0:
-        if rccl is not None:
-            rccl.close()
-        if world > 1:
-            dist.destroy_process_group()
+        finish()
         return
 
     fb_launch_ms = tk["fb_ms"] / max(1, tk["fb_launches"])
@@ -731,36 +830,9 @@ def main():
     dense_ms = tkd["fb_ms"] / max(1, tkd["fb_launches"])
     dense_fpp = fb_flops_per_pair(S, Sb, T) if split else flops_per_pair(S, Sb, d, T, cov)
     dense_ach = dense_fpp * tkd["fb_pairs"] / max(1, tkd["fb_launches"]) / (dense_ms * 1e-3) / 1e12
-    res = {
-        "metric": METRIC,
-        "value": args.steps / dt,
-        "unit": "E-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle": dict(settle, note="untimed run-ahead E-steps before the warmup steps, "
-                                    "until the clocks settle (--settle-ms)"),
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (BASELINE.md generator, seeded), resident in HBM",
-        "config": {"workload": (f"{args.config}: N={N} base HMMs, K={K} clusters, S={S} states, "
-                                f"Sb={Sb}, d={d}, {'full' if cov == 1 else 'diag'} cov, tau={T}, "
-                                f"Nv={opt['Nv']}"),
-                   "N": N, "K": K, "S": S, "Sb": Sb, "d": d, "tau": T,
-                   "parallelism": f"bases sharded over {world} GPU(s), 1 RCCL all-reduce/E-step"},
+    res.update({
         "collective": dict(
-            ({"kind": ("native RCCL communicator (vbhem_rccl_allreduce_to: all-reduce, then "
-                       "an in-stream kernel copy into the pinned statistics buffer)"
-                       if hs_dev is not None else
-                       "native RCCL communicator (vbhem_rccl_allreduce_sum, then a stream copy)"),
-              "ranks": world}
-             if rccl is not None else
-             {"kind": ("torch.distributed all_reduce (%s backend)" % backend
-                       if world > 1 else "none (one rank)"),
-              "ranks": world, "rccl_error": rccl_err}),
+            res["collective"],
             allreduce_ms=(max(a for a in per_rank_ar if a is not None)
                           if any(a is not None for a in per_rank_ar) else None),
             allreduce_ms_per_rank=per_rank_ar,
@@ -769,15 +841,7 @@ def main():
                               "ranks" % bd_steps if rccl is not None else
                               "host clock around the host-staged all-reduce with device syncs, "
                               "mean over the %d-step breakdown pass; max over ranks" % bd_steps
-                              if world > 1 else None),
-            statistics_doubles=int(stats.numel()),
-            shard_bases_per_rank=[shard_range(N, r, world)[1] - shard_range(N, r, world)[0]
-                                  for r in range(world)],
-            ms_per_step_per_rank=[s / args.steps * 1e3 for s in per_rank_s]),
-        "pacing": ("one E-step of run-ahead (the C++ EM loop's): step k+1 is enqueued before "
-                   "the host waits for step k's statistics in pinned memory"
-                   + (" -- by polling the completion word the step's last kernel writes "
-                      "(vbhem_arm_done_word)" if word is not None else " -- by an event")),
+                              if world > 1 else None)),
         "synchronous": {"value": args.steps / dts, "ms_per_step": dts / args.steps * 1e3,
                         "note": "the host waits for each step's statistics before launching "
                                 "the next (no overlap of the host hand-over)"},
@@ -863,7 +927,7 @@ def main():
         "em_iteration": em_it,
         "shard_sim": shard_sim,
         "elbo": L,
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import vbhem_oracle as vo  # cpu_baseline leg only
@@ -901,10 +965,7 @@ def main():
                                            "oracle/vbhem_oracle.c on %d host threads" % thr),
                                 "tolerance": {"LL_elbo": 1e-10, "hat_Z": 1e-5}}
     print(json.dumps(res))
-    if rccl is not None:
-        rccl.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

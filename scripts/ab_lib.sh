@@ -5,7 +5,7 @@
 set -o pipefail
 ARGS="--steps 10 --warmup 2"
 if [ "$1" = "--args" ]; then ARGS="$2"; shift 2; fi
-EXTRA="--no-cpu-baseline --no-shard-sim --em-iters 0"
+EXTRA="--full --no-cpu-baseline --no-shard-sim --em-iters 0"
 [ "$PARITY" = 1 ] || EXTRA="$EXTRA --no-parity-sample"
 for rep in 1 2; do
   for lib in tree "$@"; do

@@ -7,7 +7,7 @@ TAG=${1:-bwd4}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 [ "$NOTEST" = 1 ] || timeout -k 10 600 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > $OUT/tests.log 2>&1
 rc=$?; [ "$NOTEST" = 1 ] || tail -3 $OUT/tests.log; [ "$NOTEST" != 1 ] && [ $rc -ne 0 ] && exit $rc
-ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-parity-sample --no-shard-sim --em-iters 0"
+ARGS="--steps 10 --warmup 2 --full --no-cpu-baseline --no-parity-sample --no-shard-sim --em-iters 0"
 one() {  # label, then env assignments
   local lab=$1; shift
   env "$@" timeout -k 10 200 python bench.py $ARGS > $OUT/ab_$lab.json 2>$OUT/ab_$lab.err || return 1

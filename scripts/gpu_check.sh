@@ -8,5 +8,5 @@ if [ "$TESTS" != "none" ]; then
   timeout -k 10 900 python -u -m pytest $TESTS -x -v -m gpu --timeout 300 --timeout-method thread > $OUT/tests.log 2>&1
   rc=$?; tail -5 $OUT/tests.log; [ $rc -ne 0 ] && exit $rc
 fi
-timeout -k 10 400 python -u bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python -u bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; tail -c 3000 $OUT/bench.json; exit $rc

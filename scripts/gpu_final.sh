@@ -17,7 +17,7 @@ if [ "$NOTEST" != 1 ]; then
 fi
 for cfg in C4 C3 C5; do
   [ "$NOBENCH" = 1 ] && break
-  timeout -k 10 600 python -u bench.py --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout -k 10 600 python -u bench.py --full --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
   rc=$?; tail -c 300 $OUT/bench_$cfg.json; echo; [ $rc -ne 0 ] && exit $rc
 done
 shard() {

@@ -11,7 +11,7 @@ if [ "$NOTEST" != 1 ]; then
   rc=$?; tail -3 $OUT/tests.log; [ $rc -ne 0 ] && exit $rc
 fi
 for cfg in ${CONFIGS:-C4}; do
-  timeout -k 10 400 python -u bench.py --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout -k 10 400 python -u bench.py --full --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
   rc=$?; tail -c 400 $OUT/bench_$cfg.json; echo; [ $rc -ne 0 ] && exit $rc
 done
 [ "$NOPROF" = 1 ] && exit 0

@@ -14,7 +14,7 @@ k=0
 for g in "${GROUPS_[@]}"; do
   k=$((k+1))
   timeout -k 10 300 rocprofv3 --pmc $g -d $OUT/p$k -o p$k --output-format csv -- \
-      python3 $ROOT/bench.py --no-cpu-baseline "$@" > $OUT/p$k.log 2>&1
+      python3 $ROOT/bench.py --full --no-cpu-baseline "$@" > $OUT/p$k.log 2>&1
   rc=$?; echo "pass $k rc=$rc"; [ $rc -ne 0 ] && exit $rc
 done
 python3 - "$OUT" <<'EOF'

@@ -16,7 +16,7 @@ run() {  # name, extra rocprof args
   local name=$1; shift
   local extra=$ARGS
   case $name in pmc*) extra="$ARGS $PMC_ARGS";; trace) extra="$ARGS $TRACE_ARGS";; esac
-  timeout -k 10 300 rocprofv3 "$@" -d $OUT/$name -o $name --output-format csv -- python3 $ROOT/bench.py --no-cpu-baseline $extra > $OUT/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 "$@" -d $OUT/$name -o $name --output-format csv -- python3 $ROOT/bench.py --full --no-cpu-baseline $extra > $OUT/$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; return $rc
 }
 # the traced run skips the shard simulation too, so every launch of a kernel in the

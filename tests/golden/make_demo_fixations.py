@@ -4,8 +4,8 @@ subject index per trial, and the subject / trial names.
 
 The cells come from tests/golden/biff_cells.py, a minimal compound-file + BIFF8
 walker written separately from vbhem_amd/xls.py (the reader the fixture checks),
-with the row loop of read_xls_fixations.m:84-138.  Run in a container that has
-/root/reference mounted:
+with the row loop of read_xls_fixations.m:84-138.  The demo file itself is kept
+beside the fixture (tests/golden/demodata.xls):
 
     python tests/golden/make_demo_fixations.py
 """
@@ -17,7 +17,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import biff_cells  # noqa: E402
 
-SRC = "/root/reference/demo/demodata.xls"
+SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "demodata.xls")
 
 
 def main():

@@ -40,7 +40,9 @@ def fused_expected(base, consts, alpha, T, pairs):
                 Lt7=float((hz * np.log(hz)).sum()))
 
 
-def save_pairs_case(name, base, consts, alpha, T, want_tnu=True):
+def save_pairs_case(name, base, consts, alpha, T, want_tnu=True, part2=()):
+    """part2: array names stored in part2_<name>.npz instead (no file over 1 MiB);
+    tests/test_golden.py:load puts the two files together again."""
     pairs = vo.c_estep_pairs(base, consts, T, nthreads=4, want_tnu=want_tnu)
     fz = fused_expected(base, consts, alpha, T, pairs)
     arrays = {"in_" + k: np.asarray(base[k]) for k in ("nstates", "prior", "A", "centres", "covars",
@@ -50,6 +52,9 @@ def save_pairs_case(name, base, consts, alpha, T, want_tnu=True):
     arrays.update({"fz_" + k: np.asarray(v) for k, v in fz.items()})
     arrays.update(covmode=np.int32(base["covmode"]), T=np.int32(T), alpha=np.asarray(alpha))
     path = os.path.join(HERE, f"{name}.npz")
+    if part2:
+        np.savez_compressed(os.path.join(HERE, f"part2_{name}.npz"),
+                            **{k: arrays.pop(k) for k in part2})
     np.savez_compressed(path, **arrays)
     return path
 
@@ -69,7 +74,7 @@ def main():
     # C5-shaped (full, d=16, S=Sb=12, K=32), 1 base
     cs = make_case(1, 32, 12, 12, 16, 1, seed=505, tau=10)
     out.append(save_pairs_case("pairs_c5", cs["base"], cs["consts"], cs["post"]["alpha"], 10,
-                               want_tnu=False))
+                               want_tnu=False, part2=("out_emit_Mu",)))
     # EM trajectory: full C2 config (N=100), oracle loop-style EM to convergence
     base, P, opt = vb.synth_workload("C2")
     b = base.numpy()

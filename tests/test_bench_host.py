@@ -32,6 +32,29 @@ def test_committed_traffic_takes_newest_tag(tmp_path, monkeypatch):
     assert bench.committed_traffic("C4", 100000, 2, "vbhem::fb_bwd4_kernel") == (None, None)
 
 
+def test_dump_outputs_writes_float64_and_samples_large_arrays(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; one over the byte limit
+    is cut to the same ascending sample of its rows in every run."""
+    import numpy as np
+    import torch
+
+    import bench
+    small = torch.arange(7, dtype=torch.float64)
+    big = torch.arange(100 * 4, dtype=torch.float64).view(100, 4)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"stats": small, "L_elbo": big},
+                                max_bytes=10 * 4 * 8)
+    assert shapes == {"stats": [[7], [7]], "L_elbo": [[10, 4], [100, 4]]}
+    s, b = np.load(tmp_path / "a" / "stats.npy"), np.load(tmp_path / "a" / "L_elbo.npy")
+    assert s.dtype == b.dtype == np.float64
+    np.testing.assert_array_equal(s, small.numpy())
+    rows = (b[:, 0] / 4).astype(int)
+    assert (np.diff(rows) > 0).all() and 0 <= rows[0] and rows[-1] < 100
+    np.testing.assert_array_equal(b, big.numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "b"), {"L_elbo": big}, max_bytes=10 * 4 * 8)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "L_elbo.npy"), b)
+    assert 3 * bench.DUMP_BYTES_PER_ARRAY <= 64 * 10 ** 6
+
+
 def test_resolve_world_launches_or_runs_as_rank():
     """--gpus N without WORLD_SIZE starts N ranks; under a launcher the rank count is
     WORLD_SIZE and a disagreeing --gpus is refused."""

@@ -2,7 +2,7 @@
 place of xlsread) and the demo's data path into the VB-HMM forward-backward.
 
 CPU: RK-number and shared-string decoding on hand-built records; the reference's
-demo/demodata.xls (when /root/reference is mounted) against the committed
+demo/demodata.xls (kept as tests/golden/demodata.xls) against the committed
 fixture tests/golden/demo_fixations.npz.  The fixture is made by
 make_demo_fixations.py from tests/golden/biff_cells.py, a second reader written
 separately from vbhem_amd/xls.py (compound file + SST/LABELSST/NUMBER/RK/MULRK
@@ -23,7 +23,7 @@ from conftest import GOLDEN_DIR, rel_err
 sys.path.insert(0, GOLDEN_DIR)
 import biff_cells  # noqa: E402  (the independent reader; test infrastructure)
 
-DEMO = "/root/reference/demo/demodata.xls"
+DEMO = os.path.join(GOLDEN_DIR, "demodata.xls")
 
 
 def test_rk_decoding(vb):
@@ -58,8 +58,6 @@ def test_independent_reader_decodes_the_same(vb):
 
 def test_fixture_from_independent_reader(vb):
     """The committed fixture is what biff_cells reads from the demo file."""
-    if not os.path.exists(DEMO):
-        pytest.skip("reference demo data not mounted")
     fx = np.load(os.path.join(GOLDEN_DIR, "demo_fixations.npz"))
     data, names, trials = biff_cells.read_fixations(DEMO)
     seqs = [t for subj in data for t in subj]
@@ -72,8 +70,6 @@ def test_demo_file_matches_fixture(vb):
     fx = np.load(os.path.join(GOLDEN_DIR, "demo_fixations.npz"))
     assert fx["offsets"][-1] == fx["x"].shape[0] == 1010
     assert len(fx["names"]) == 10 and fx["offsets"].size - 1 == 399
-    if not os.path.exists(DEMO):
-        pytest.skip("reference demo data not mounted")
     from vbhem_amd.xls import read_xls_fixations
     data, names, trials = read_xls_fixations(DEMO)
     seqs = [t for subj in data for t in subj]
