@@ -56,6 +56,11 @@ class HmmParamsT(ctypes.Structure):  # include/vbhmm_fb.h vbhmm_params_t
                 ("const_denominator", ctypes.c_double)]
 
 
+class ScoreHmmsT(ctypes.Structure):  # include/vbhmm_score.h vbhmm_score_hmms_t
+    _fields_ = [("H", _c_int), ("KM", _c_int), ("dim", _c_int), ("covmode", _c_int),
+                ("nstates", _vp), ("prior", _vp), ("trans", _vp), ("mean", _vp), ("cov", _vp)]
+
+
 class EmExtT(ctypes.Structure):  # include/vbhem_em.h vbhem_em_ext_t
     _fields_ = [("rccl_comm", _vp), ("iter_seconds", _vp), ("calc_deriv", _c_int), ("dLL", _vp)]
 
@@ -139,6 +144,12 @@ EXPORTS = {
                           _c_size, _vp]),
     "vbhmm_fb_host": (_c_int, [_c_int, ctypes.POINTER(SeqsT), ctypes.POINTER(HmmParamsT), _vp, _vp,
                                _vp, _vp]),
+    "vbhmm_score_prepared_bytes": (_c_size, [ctypes.POINTER(ScoreHmmsT)]),
+    "vbhmm_score_prepare": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, _c_size, _vp]),
+    "vbhmm_score_workspace_bytes": (_c_size, [ctypes.POINTER(ScoreHmmsT), ctypes.c_longlong]),
+    "vbhmm_score_ll": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT), _vp, _vp]),
+    "vbhmm_score_viterbi": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT),
+                                     ctypes.c_longlong, _vp, _vp, _vp, _c_size, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),
