@@ -150,6 +150,11 @@ EXPORTS = {
     "vbhmm_score_ll": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT), _vp, _vp]),
     "vbhmm_score_viterbi": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT),
                                      ctypes.c_longlong, _vp, _vp, _vp, _c_size, _vp]),
+    "vbhmm_ppk_prepared_bytes": (_c_size, [ctypes.POINTER(ScoreHmmsT)]),
+    "vbhmm_ppk_prepare": (_c_int, [ctypes.POINTER(ScoreHmmsT), ctypes.c_double, ctypes.c_double, _vp,
+                                   _c_size, _vp]),
+    "vbhmm_ppk_gram": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(ScoreHmmsT), _vp,
+                                _c_int, _c_int, _vp, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),

@@ -1,0 +1,154 @@
+// tests/ppkcheck/ppkcheck.hip -- TEST-ONLY exports of the probability product kernel
+// arithmetic (csrc/vbhmm_ppk_pair.h): a host loop over HMM pairs calling the
+// routines the kernels call, so the logic is checked on a machine without a GPU,
+// and the same call through the library's kernels on device 0.  Arrays are host
+// arrays in the layouts of include/vbhmm_score.h; the sets a and b share the
+// dimension and the covariance mode.  out: [Ha][Hb] (modes 0, 1) or [Ha] (mode 2).
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "vbhmm_ppk.h"
+#include "vbhmm_ppk_pair.h"
+
+namespace {
+
+using namespace vbhem::ppk;
+
+struct Set {
+  int H, KM;
+  const int *nstates;
+  const double *prior, *trans, *mean, *cov;
+};
+
+struct HostPrep {
+  const Set &s;
+  int d;
+  bool diag;
+  double rho, pad;
+  const Layout &L;
+  std::vector<double> &blocks;
+  template <int KB, int DB>
+  long long operator()() const {
+    const size_t cs = diag ? (size_t)d : (size_t)d * d;
+    long long bad = 0;
+    for (int h = 0; h < s.H; ++h)
+      for (int k = 0; k < s.KM; ++k)
+        if (!prepare_state<DB>(L, blocks.data() + (size_t)h * L.stride, k, s.nstates[h], d, diag, rho, pad,
+                               s.prior + (size_t)h * s.KM, s.trans + (size_t)h * s.KM * s.KM,
+                               s.mean + (size_t)h * s.KM * d, s.cov + (size_t)h * s.KM * cs) &&
+            !bad)
+          bad = 1 + (long long)h * s.KM + k;
+    return bad;
+  }
+};
+
+struct HostGram {
+  const Layout &La, &Lb;
+  const std::vector<double> &ba, &bb;
+  int Ha, Hb, d, T, mode;
+  double *out;
+  template <int KB, int DB>
+  long long operator()() const {
+    for (int i = 0; i < Ha; ++i)
+      for (int j = 0; j < Hb; ++j) {
+        if ((mode == VBHMM_PPK_DIAG && i != j) || (mode == VBHMM_PPK_SYM && i > j)) continue;
+        const double v = pair_kernel<KB, DB>(view(La, ba.data() + (size_t)i * La.stride),
+                                             view(Lb, bb.data() + (size_t)j * Lb.stride), d, T);
+        if (mode == VBHMM_PPK_DIAG) {
+          out[i] = v;
+        } else {
+          out[(size_t)i * Hb + j] = v;
+          if (mode == VBHMM_PPK_SYM) out[(size_t)j * Hb + i] = v;
+        }
+      }
+    return 0;
+  }
+};
+
+struct DevSet {
+  void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  void *prep = nullptr;
+  vbhmm_score_hmms_t m{};
+  size_t pb = 0;
+};
+
+hipError_t upload(const Set &s, int d, int covmode, DevSet &v) {
+  const size_t cs = covmode == VBHEM_COV_DIAG ? (size_t)d : (size_t)d * d;
+  const size_t bytes[] = {(size_t)s.H * sizeof(int), (size_t)s.H * s.KM * 8, (size_t)s.H * s.KM * s.KM * 8,
+                          (size_t)s.H * s.KM * d * 8, (size_t)s.H * s.KM * cs * 8};
+  const void *host[] = {s.nstates, s.prior, s.trans, s.mean, s.cov};
+  hipError_t e = hipSuccess;
+  for (int q = 0; q < 5 && e == hipSuccess; ++q) {
+    e = hipMalloc(&v.p[q], bytes[q] + 8);
+    if (e == hipSuccess && bytes[q]) e = hipMemcpy(v.p[q], host[q], bytes[q], hipMemcpyHostToDevice);
+  }
+  v.m = {s.H, s.KM, d, covmode, static_cast<const int *>(v.p[0]), static_cast<const double *>(v.p[1]),
+         static_cast<const double *>(v.p[2]), static_cast<const double *>(v.p[3]),
+         static_cast<const double *>(v.p[4])};
+  v.pb = vbhmm_ppk_prepared_bytes(&v.m);
+  if (e == hipSuccess) e = hipMalloc(&v.prep, v.pb + 8);
+  return e;
+}
+
+void release(DevSet &v) {
+  for (void *q : v.p) (void)hipFree(q);
+  (void)hipFree(v.prep);
+}
+
+}  // namespace
+
+extern "C" {
+
+// 0, or 1 + (h KM + k) of the first regularised covariance of set a that is not
+// positive definite, or -(1 + ...) of set b.
+long long ppkcheck_host(int d, int covmode, double rho, double pad, int T, int mode, int Ha, int KMa,
+                        const int *nstates_a, const double *prior_a, const double *trans_a,
+                        const double *mean_a, const double *cov_a, int Hb, int KMb, const int *nstates_b,
+                        const double *prior_b, const double *trans_b, const double *mean_b,
+                        const double *cov_b, double *out) {
+  const Set sa{Ha, KMa, nstates_a, prior_a, trans_a, mean_a, cov_a};
+  const Set sb{Hb, KMb, nstates_b, prior_b, trans_b, mean_b, cov_b};
+  const Layout La = make_layout(KMa, d), Lb = make_layout(KMb, d);
+  const bool diag = covmode == VBHEM_COV_DIAG;
+  std::vector<double> ba((size_t)Ha * La.stride, 0.0), bb((size_t)Hb * Lb.stride, 0.0);
+  long long bad = dispatch(KMa, d, HostPrep{sa, d, diag, rho, pad, La, ba});
+  if (bad) return bad;
+  bad = dispatch(KMb, d, HostPrep{sb, d, diag, rho, pad, Lb, bb});
+  if (bad) return -bad;
+  return dispatch(KMa > KMb ? KMa : KMb, d, HostGram{La, Lb, ba, bb, Ha, Hb, d, T, mode, out});
+}
+
+// The same through vbhmm_ppk_prepare / vbhmm_ppk_gram on device 0 (mode 1: set a on
+// both sides).  Returns the library's status, or a positive hipError_t of the copies.
+int ppkcheck_device(int d, int covmode, double rho, double pad, int T, int mode, int Ha, int KMa,
+                    const int *nstates_a, const double *prior_a, const double *trans_a,
+                    const double *mean_a, const double *cov_a, int Hb, int KMb, const int *nstates_b,
+                    const double *prior_b, const double *trans_b, const double *mean_b,
+                    const double *cov_b, double *out) {
+  const Set sa{Ha, KMa, nstates_a, prior_a, trans_a, mean_a, cov_a};
+  const Set sb{Hb, KMb, nstates_b, prior_b, trans_b, mean_b, cov_b};
+  const bool sym = mode == VBHMM_PPK_SYM;
+  const size_t out_bytes = (mode == VBHMM_PPK_DIAG ? (size_t)Ha : (size_t)Ha * Hb) * 8;
+  DevSet da, db;
+  void *dout = nullptr;
+  int rc = 0;
+  hipError_t e = upload(sa, d, covmode, da);
+  if (e == hipSuccess && !sym) e = upload(sb, d, covmode, db);
+  if (e == hipSuccess) e = hipMalloc(&dout, out_bytes + 8);
+  if (e == hipSuccess) {
+    rc = vbhmm_ppk_prepare(&da.m, rho, pad, da.prep, da.pb, nullptr);
+    if (rc == 0 && !sym) rc = vbhmm_ppk_prepare(&db.m, rho, pad, db.prep, db.pb, nullptr);
+    if (rc == 0)
+      rc = vbhmm_ppk_gram(&da.m, da.prep, sym ? &da.m : &db.m, sym ? da.prep : db.prep, T, mode,
+                          static_cast<double *>(dout), nullptr);
+    if (rc == 0) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess && rc == 0 && out_bytes) e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  release(da);
+  release(db);
+  (void)hipFree(dout);
+  return rc != 0 ? rc : (int)e;
+}
+
+}  // extern "C"
