@@ -90,6 +90,15 @@ EXPORTS = {
                                                      _c_int, _c_int]),
     "vbhem_estep_fused_trials": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(ClusterT), _c_int,
                                           _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "vhem_fused_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), ctypes.POINTER(ClusterT), _c_int]),
+    "vhem_fused_trials_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), ctypes.POINTER(ClusterT),
+                                                    _c_int, _c_int]),
+    "vhem_estep_fused": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(ClusterT), _c_int,
+                                  ctypes.c_double, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp,
+                                  _vp, _c_size, _vp]),
+    "vhem_estep_fused_trials": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(ClusterT), _c_int,
+                                         _c_int, ctypes.c_double, _vp, _vp, ctypes.c_double, _vp,
+                                         _vp, _vp, _vp, _vp, _c_size, _vp]),
     "vbhem_last_fallback_count": (_c_int, [_vp, _vp]),
     "vbhem_host_device_pointer": (_c_int, [_vp, ctypes.POINTER(_vp)]),
     "vbhem_arm_done_word": (_c_int, [_vp, ctypes.c_ulonglong]),

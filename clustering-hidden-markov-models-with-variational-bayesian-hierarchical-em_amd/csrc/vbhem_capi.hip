@@ -454,8 +454,13 @@ struct FbCtx {
   double *u_ws = nullptr;
 };
 
+// split_first_pass (the VHEM fused call): the gated schedule's backward-only pass runs on
+// fb_split_kernel's backward mode, whose L_elbo has the dense schedule's rounding, not on
+// fb_bwd2 / fb_bwd4 / fb_bwd12_kernel.  VHEM multiplies L_elbo by N_i / inf_norm (up to
+// hundreds) before the softmax, so the few ulp that the reduced-operation exp / log of
+// those kernels cost show in Z, Nj and the statistics.
 int prepare_fb(FbCtx &c, const vbhem_base_t *b, const vbhem_cluster_t *cl, int T,
-               double smooth = 1.0) {
+               double smooth = 1.0, bool split_first_pass = false) {
   c.split = plan_split(b->SB, b->d, b->covmode, cl->K, cl->S, T, vbhem::split_lpc(cl->S));
   // backward-only pass: half the lanes per column (no forward-sweep registers to
   // hold), more rows per lane: no DPP for S <= 8, more independent exp/log chains
@@ -491,11 +496,13 @@ int prepare_fb(FbCtx &c, const vbhem_base_t *b, const vbhem_cluster_t *cl, int T
     vbhem::SplitArgs &ab = c.bwd.a;
     ab.prior = b->prior; ab.A = b->A; ab.logA = cl->logA; ab.logPi = cl->logPi;
     if (c.bwd.ok && cl->S <= vbhem::kBwd2MaxS && !std::getenv("VBHEM_NO_BWD2")) {
-      c.bwd2_nwb = vbhem::bwd2_waves(cl->S);
-      c.bwd2_lds = vbhem::bwd2_lds(cl->S, c.bwd2_nwb);
-      c.bwd2_ppb = vbhem::bwd2_ppb(cl->S, c.bwd2_nwb);
-      c.bwd4 = vbhem::bwd4_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD4");
-      c.bwd12 = vbhem::bwd12_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD12");
+      if (!split_first_pass) {
+        c.bwd2_nwb = vbhem::bwd2_waves(cl->S);
+        c.bwd2_lds = vbhem::bwd2_lds(cl->S, c.bwd2_nwb);
+        c.bwd2_ppb = vbhem::bwd2_ppb(cl->S, c.bwd2_nwb);
+        c.bwd4 = vbhem::bwd4_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD4");
+        c.bwd12 = vbhem::bwd12_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD12");
+      }
       c.list4 = vbhem::list4_supported(cl->S, b->SB, T, cl->K) && !std::getenv("VBHEM_NO_LIST4");
       c.list12 = vbhem::list12_supported(cl->S, b->SB, T, cl->K) && !std::getenv("VBHEM_NO_LIST12");
     }
@@ -935,23 +942,37 @@ int vbhem_done_word_free(void *host_ptr) {
   return e == hipSuccess ? VBHEM_OK : hip_fail(e, "hipHostFree(done word)");
 }
 
-int vbhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
-                             const double *tildeN_dev, const double *logOmega_dev,
-                             double *stats_dev, double *hatZ_dev, double *LL_elbo_dev,
-                             void *workspace_dev, size_t workspace_bytes, void *stream) {
+// the VHEM mode of the fused call (vhem_estep_fused*): null for VBHEM
+struct VhemIn {
+  double smooth, inf_norm;
+  const double *omegaB;
+};
+
+static int fused_impl(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
+                      const double *tildeN_dev, const double *logOmega_dev, double *stats_dev,
+                      double *hatZ_dev, double *LL_elbo_dev, void *workspace_dev,
+                      size_t workspace_bytes, void *stream, const VhemIn *vh) {
   // (taken first: a call that fails leaves nothing armed for the next one)
   unsigned long long *const done_word = g_done_word.exchange(nullptr);
   const unsigned long long done_val = g_done_val.load();
   int rc = check_inputs(base, clus, T);
   if (rc != VBHEM_OK) return rc;
+  if (vh) {
+    if (!(vh->smooth > 0.0) || !std::isfinite(vh->smooth))
+      return fail(VBHEM_ERR_ARG, "smooth must be a positive finite number");
+    if (!(vh->inf_norm > 0.0) || !std::isfinite(vh->inf_norm))
+      return fail(VBHEM_ERR_ARG, "inf_norm must be a positive finite number");
+    if (base->N > 0 && !vh->omegaB) return fail(VBHEM_ERR_ARG, "null fused argument");
+  }
   if (R < 1 || clus->K % R != 0)
     return fail(VBHEM_ERR_ARG, "trials: K must be a positive multiple of R");
-  if (R > 1 && clus->K > 256)
+  if (!vh && R > 1 && clus->K > 256)  // (resp_trials_kernel; vhem_resp_kernel has no such limit)
     return fail(VBHEM_ERR_UNSUPPORTED, "trials: at most 256 clusters in total (R * K_trial)");
   if (!logOmega_dev || !stats_dev ||
       (base->N > 0 && (!tildeN_dev || !hatZ_dev || !LL_elbo_dev)))
     return fail(VBHEM_ERR_ARG, "null fused argument");
-  if (vbhem::resp_lds(clus->K, clus->K / R) > kLdsLimit)
+  if ((vh ? vbhem::vhem_resp_lds(clus->K, clus->K / R) : vbhem::resp_lds(clus->K, clus->K / R)) >
+      kLdsLimit)
     return fail(VBHEM_ERR_UNSUPPORTED, "fused: too many clusters for the responsibilities "
                                        "kernel (K <= ~2,400)");
   FusedWs w;
@@ -972,12 +993,17 @@ int vbhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *cl
   sa.centres = base->centres; sa.covars = base->covars; sa.LL = LL_elbo_dev;
   sa.nu1 = w.nu1; sa.xi = w.xi; sa.tnu = w.tnu; sa.tildeN = tildeN_dev; sa.logOmega = logOmega_dev;
   sa.Z = w.Z; sa.hatZ = hatZ_dev; sa.slabs = w.slabs;
+  if (vh) {  // Z: the weights w = Z omega_b; hatZ: Z (vhem_resp_kernel)
+    sa.vhem = 1;
+    sa.omegaB = vh->omegaB;
+    sa.inf_norm = vh->inf_norm;
+  }
   size_t slds = 0;
   int ngroups = 1;
   const bool dense_ok = vbhem::plan_stats(sa, slds, ngroups);  // dense-schedule statistics
 
   FbCtx ctx;
-  rc = prepare_fb(ctx, base, clus, T);
+  rc = prepare_fb(ctx, base, clus, T, vh ? vh->smooth : 1.0, vh != nullptr);
   if (rc != VBHEM_OK) return rc;
   ctx.u_ws = w.U;
   // gated schedule: split kernel + list statistics tile must apply
@@ -1096,6 +1122,43 @@ int vbhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *cl
   if (e != hipSuccess) return hip_fail(e, "stats_final_kernel");
   guard.fpre = nullptr;
   return VBHEM_OK;
+}
+
+int vbhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
+                             const double *tildeN_dev, const double *logOmega_dev,
+                             double *stats_dev, double *hatZ_dev, double *LL_elbo_dev,
+                             void *workspace_dev, size_t workspace_bytes, void *stream) {
+  return fused_impl(base, clus, R, T, tildeN_dev, logOmega_dev, stats_dev, hatZ_dev, LL_elbo_dev,
+                    workspace_dev, workspace_bytes, stream, nullptr);
+}
+
+size_t vhem_fused_workspace_bytes(const vbhem_base_t *base, const vbhem_cluster_t *clus, int T) {
+  return vbhem_fused_trials_workspace_bytes(base, clus, 1, T);
+}
+
+size_t vhem_fused_trials_workspace_bytes(const vbhem_base_t *base, const vbhem_cluster_t *clus,
+                                         int R, int T) {
+  return vbhem_fused_trials_workspace_bytes(base, clus, R, T);
+}
+
+int vhem_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int T, double smooth,
+                     const double *Ni_dev, const double *omegaB_dev, double inf_norm,
+                     const double *logOmega_dev, double *stats_dev, double *Z_dev,
+                     double *LL_elbo_dev, void *workspace_dev, size_t workspace_bytes,
+                     void *stream) {
+  return vhem_estep_fused_trials(base, clus, 1, T, smooth, Ni_dev, omegaB_dev, inf_norm,
+                                 logOmega_dev, stats_dev, Z_dev, LL_elbo_dev, workspace_dev,
+                                 workspace_bytes, stream);
+}
+
+int vhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
+                            double smooth, const double *Ni_dev, const double *omegaB_dev,
+                            double inf_norm, const double *logOmega_dev, double *stats_dev,
+                            double *Z_dev, double *LL_elbo_dev, void *workspace_dev,
+                            size_t workspace_bytes, void *stream) {
+  const VhemIn vh{smooth, inf_norm, omegaB_dev};
+  return fused_impl(base, clus, R, T, Ni_dev, logOmega_dev, stats_dev, Z_dev, LL_elbo_dev,
+                    workspace_dev, workspace_bytes, stream, &vh);
 }
 
 int vbhem_set_fused_mode(int mode) {

@@ -1096,7 +1096,8 @@ hipError_t launch_emission(const EmissionArgs &a, size_t lds, hipStream_t st) {
     // W' restaged per chunk: two column tiles per wave halve the staging per column
     if (a.kdp / 4 == 38) {  // d = 16 full (C5)
       // double-buffered chunks with buffer stores (E below 4 GB; VBHEM_EM_NODB: A/B)
-      if (em_bst_ok(a) && (a.ksp / 16) % 4 == 0 && !std::getenv("VBHEM_EM_NODB"))
+      // (emission_db_kernel has no E /= smooth: the VHEM calls take emission_u_kernel)
+      if (a.smooth == 1.0 && em_bst_ok(a) && (a.ksp / 16) % 4 == 0 && !std::getenv("VBHEM_EM_NODB"))
         return launch_db_fn<38, 2, 2>(a, st);
       return launch_u_fn<38, 4, UNTW, true>(a, lds, st);
     }

@@ -133,6 +133,11 @@ struct StatsArgs {
   double *xscratch;          // its scratch: xslots slots of xstride doubles
   long long xstride;
   int xslots;
+  // VHEM mode (vhem != 0; vhem_resp_kernel, and the w > 0 gate of the consumers): Z is
+  // the weight buffer w = Z omega_b, hatZ the responsibilities Z, tildeN = N_i
+  int vhem;
+  const double *omegaB;      // [N] omega_b
+  double inf_norm;           // L_elbo /= inf_norm (hem_h3m_c_step.m:110-119, 293)
 };
 
 // fb_split_kernel (one base-state column per LPC lanes; S <= kSplitMaxS, SB <= S).
@@ -453,6 +458,7 @@ bool plan_stats_list(StatsArgs &a, size_t &lds);
 hipError_t launch_gate_list(const StatsArgs &a, int nchunk, hipStream_t st);
 size_t gate_list_lds(int K);  // dynamic LDS of gate_list_kernel for K clusters
 size_t resp_lds(int K, int KT);  // dynamic LDS of resp_kernel / resp_trials_kernel
+size_t vhem_resp_lds(int K, int KT);  // dynamic LDS of vhem_resp_kernel
 // *stats_slabs (optional): the slabs [0, n) holding this launch's N1 / M / U entries
 hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStream_t st,
                              int *stats_slabs = nullptr);

@@ -5,6 +5,9 @@
 //                      and the per-chunk partial sums Nj = sum_i Z (:282),
 //                      Lt1 = sum Z .* L_elbo, Lt7 = sum hat_Z .* log(hat_Z)
 //                      (vbhemh3m_lb.m:90, 107).
+//   vhem_resp_kernel   the VHEM mode's responsibilities Z, weights w = Z omega_b and
+//                      partial sums Nj, LogL (hem_h3m_c_step.m:293-314, 430, 443); the
+//                      kernels below then sum under its gate w > 0 (Gate<kGateVhem>)
 //   nm_kernel          streaming weighted sums over this chunk's bases
 //                      (vbhem_compute_Statistics.m:33-55, gate Z > 1e-8):
 //                        N1[j][s]    += g Z(i,j) sum_nu_1(i,j,s)
@@ -65,6 +68,16 @@ __device__ __forceinline__ void chunk_range(int nb, int i_begin, int chunk, int 
 }  // namespace
 
 constexpr double kGateZ = 1e-8;  // vbhem_compute_Statistics.m:35  (Z_Ni(i) > 1e-8)
+// The gate of the statistic sums is a compile-time parameter of the kernels that apply
+// it to the weight buffer StatsArgs::Z (gate_list_kernel, stats_kernel, nm_kernel; the
+// stats_list_* kernels read the lists and the weights only):
+//   kGateVbhem  weight = Z = hat_Z tilde_N, gate Z > 1e-8
+//   kGateVhem   weight = w = Z omega_b,     gate w > 0   (hem_mstep_component.m:88)
+constexpr int kGateVbhem = 0, kGateVhem = 1;
+template <int GM>
+struct Gate {
+  static constexpr double value = GM == kGateVhem ? 0.0 : kGateZ;
+};
 
 // ---------------------------------------------------------------------------
 // resp_kernel: one wavefront per base (lanes over clusters j).
@@ -412,6 +425,111 @@ __global__ __launch_bounds__(kRespThreads) void resp_trials_kernel(const StatsAr
 }
 
 // ---------------------------------------------------------------------------
+// vhem_resp_kernel: the VHEM responsibilities (hem_h3m_c_step.m:293-314) of R = K / KT
+// independent EM trials (R = 1: one cluster set), per base i and trial r:
+//   Ls = L_elbo(i, j) / inf_norm,  lz = log omega_j + N_i Ls   (each rounded as written)
+//   mx = max_j lz, sm = sum_j exp(lz - mx), lse = mx + log(sm),
+//   Z = exp(lz - mx) / sm = exp(lz - lse)  (no 1e-50; log omega = -inf gives exactly 0.
+//   The quotient form keeps every row's sum within a few ulp of 1 whatever |lz| is;
+//   exp(lz - lse) carries ulp(lse) -- 1e-13 at |lz| ~ 1e3 -- into every entry.)
+//   w = Z omega_b(i)  -> the weight buffer StatsArgs::Z,  Z -> StatsArgs::hatZ
+// and the per-chunk partial sums Nj = sum_i Z (:430), LogL = sum_i lse (:308) and the
+// counts of pairs with w > 0.  A wavefront owns the bases b0 + wave, b0 + wave + NW, ...
+// of its chunk, in ascending order; its 64 / G groups of G lanes (G the power of two
+// >= KT, <= 64) take the trials r = sub, sub + 64 / G, ... of that base, a lane the
+// clusters gl, gl + G, ... of the trial (KT = G: a cluster per lane; KT < G: the lanes
+// past KT masked; KT > 64: the loop).  Every (trial, cluster) sum is therefore the sum
+// over a wavefront's bases in ascending order, then over the wavefronts in order: the
+// same bits whatever R is (a trial batched with others equals the trial alone), no
+// atomics on doubles.  The folded exact fallback as in resp_kernel.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kRespThreads) void vhem_resp_kernel(const StatsArgs p) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = kRespThreads / 64;
+  const int K = p.K, KT = p.KT, R = K / KT, SL = p.SL, S = p.S;
+  int G = 1;
+  while (G < KT && G < 64) G <<= 1;
+  const int TPS = 64 / G;  // trials per wave step
+  const int sub = lane / G, gl = lane - sub * G;
+  double *accNj = lds;                 // [NW][K]
+  double *accL = accNj + NW * K;       // [NW][R]
+  int *gcnt = reinterpret_cast<int *>(accL + NW * R);  // [K]
+  int b0, b1;
+  chunk_range(p.i_end - p.i_begin, p.i_begin, blockIdx.x, gridDim.x, b0, b1);
+  if (p.fold) {  // (see resp_kernel)
+    int *fc = p.fx.flag_count;
+    const int cnt = __atomic_load_n(fc, __ATOMIC_RELAXED);
+    if (blockIdx.x == 0 && tid == 0) fc[3] = cnt;
+    if (cnt > 0) {  // block-uniform
+      const int nw = min(kRespFoldWaves, max(1, p.xslots / (int)gridDim.x));
+      int *q = reinterpret_cast<int *>(lds), *qn = q + kRespThreads;
+      auto mine = [&](int pair) { const int i = pair / K; return i >= b0 && i < b1; };
+      if (exact_wave_in_lds(p.fx.S, p.fx.SB))
+        fold_exact<false>(p.fx, 0, cnt, mine, p.xscratch, p.xstride, (int)blockIdx.x * nw, nw, q, qn,
+                          lds + fold_lds_bytes(kRespThreads, 0, 1, 1) / sizeof(double));
+      else
+        fold_exact<true>(p.fx, 0, cnt, mine, p.xscratch, p.xstride, (int)blockIdx.x * nw, nw, q, qn,
+                         nullptr);
+    }
+  }
+  for (int x = tid; x < NW * K + NW * R; x += kRespThreads) accNj[x] = 0.0;
+  for (int x = tid; x < K; x += kRespThreads) gcnt[x] = 0;
+  __syncthreads();
+  const double inf_norm = p.inf_norm;
+  for (int i = b0 + wave; i < b1; i += NW) {  // wave-uniform
+#pragma clang fp contract(off)
+    const double ni = p.tildeN[i], ob = p.omegaB[i];
+    const double *LL = p.LL + (size_t)i * K;
+    for (int r0 = 0; r0 < R; r0 += TPS) {  // wave-uniform
+      const int r = r0 + sub;
+      const bool rv = r < R;
+      const int jb = (rv ? r : 0) * KT;
+      double mx = -INFINITY;
+      for (int j = gl; j < KT; j += G)
+        mx = fmax(mx, p.logOmega[jb + j] + ni * (LL[jb + j] / inf_norm));
+      mx = group_max(mx, G);
+      double sm = 0.0;
+      for (int j = gl; j < KT; j += G)
+        sm += exp((p.logOmega[jb + j] + ni * (LL[jb + j] / inf_norm)) - mx);
+      sm = group_sum(sm, G);
+      const double lse = mx + log(sm);
+      if (rv) {
+        for (int j = gl; j < KT; j += G) {
+          const double lz = p.logOmega[jb + j] + ni * (LL[jb + j] / inf_norm);
+          const double Z = exp(lz - mx) / sm;
+          const double w = Z * ob;
+          p.hatZ[(size_t)i * K + jb + j] = Z;
+          p.Z[(size_t)(i - p.i_buf0) * K + jb + j] = w;
+          accNj[wave * K + jb + j] += Z;
+          if (w > Gate<kGateVhem>::value) atomicAdd(&gcnt[jb + j], 1);
+        }
+        if (gl == 0) accL[wave * R + r] += lse;
+      }
+    }
+  }
+  __syncthreads();
+  double *slab = p.slabs + (size_t)blockIdx.x * p.slab_len;
+  for (int j = tid; j < K; j += kRespThreads) {
+    double s = 0.0;
+    for (int w = 0; w < NW; ++w) s += accNj[w * K + j];
+    const int r = j / KT;
+    double &dst = slab[(size_t)r * SL + (j - r * KT)];
+    dst = p.assign ? s : dst + s;
+  }
+  for (int x = tid; x < 2 * R; x += kRespThreads) {
+    const int r = x >> 1, q = x & 1;
+    double s = 0.0;
+    if (q == 0)
+      for (int w = 0; w < NW; ++w) s += accL[w * R + r];
+    double &dst = slab[(size_t)r * SL + KT + (size_t)KT * S + (size_t)KT * S * S + q];
+    dst = p.assign ? s : dst + s;
+  }
+  if (p.gate_cnt)
+    for (int j = tid; j < K; j += kRespThreads) p.gate_cnt[(size_t)blockIdx.x * K + j] = gcnt[j];
+}
+
+// ---------------------------------------------------------------------------
 // gate_list_kernel: the gated pairs as per-cluster lists of bases, ascending i
 // (list[j][n], n < list_tot[j]).  Block = the resp_kernel chunk: its offset in
 // cluster j's list is the gate count of the chunks before it; inside the chunk
@@ -420,6 +538,7 @@ __global__ __launch_bounds__(kRespThreads) void resp_trials_kernel(const StatsAr
 // ---------------------------------------------------------------------------
 constexpr int kListThreads = 256;
 
+template <int GM>
 __global__ __launch_bounds__(kListThreads) void gate_list_kernel(const StatsArgs p) {
   extern __shared__ int ish[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -488,7 +607,7 @@ __global__ __launch_bounds__(kListThreads) void gate_list_kernel(const StatsArgs
       for (int q = 0; q < kJB; ++q) z[q] = j0 + q < K ? Zi[j0 + q] : 0.0;
 #pragma unroll
       for (int q = 0; q < kJB; ++q) {
-        const unsigned long long m = __ballot(iv && z[q] > kGateZ);
+        const unsigned long long m = __ballot(iv && z[q] > Gate<GM>::value);
         if (lane == 0 && j0 + q < K) msk[wave * K + j0 + q] = m;
       }
     }
@@ -643,7 +762,7 @@ constexpr int kStatsMaxNBB = 4;
 constexpr int kStatsMaxA = 8;   // sum_t_nu values per thread per batch
 constexpr int kStatsMaxR = 8;   // raw covariance / mean values per thread per batch
 
-template <int TPW>
+template <int TPW, int GM>
 __global__ __launch_bounds__(kStatsThreads) void stats_kernel(const StatsArgs p) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -729,7 +848,7 @@ __global__ __launch_bounds__(kStatsThreads) void stats_kernel(const StatsArgs p)
   for (int ib = b0; ib < b1; ib += NBB) {
     const int nq = min(NBB, b1 - ib);
     // -- commit: gated Z and the raw base data of this batch -> LDS ------------------
-    if (tid < NBB * JGc) gzs[tid] = (pz > kGateZ) ? pz : 0.0;
+    if (tid < NBB * JGc) gzs[tid] = (pz > Gate<GM>::value) ? pz : 0.0;
 #pragma unroll
     for (int e = 0; e < kStatsMaxR; ++e) {
       const int x = tid + e * kStatsThreads;
@@ -813,7 +932,7 @@ __global__ __launch_bounds__(kStatsThreads) void stats_kernel(const StatsArgs p)
 constexpr int kNmThreads = 256;
 
 // PER outputs per thread (K*S + K*S*S <= PER * 256), UNR bases per step in flight.
-template <int PER, int UNR>
+template <int PER, int UNR, int GM>
 __global__ __launch_bounds__(kNmThreads) void nm_kernel(const StatsArgs p) {
   const int tid = threadIdx.x;
   const int K = p.K, S = p.S, KS = K * S, KSS = KS * S, NO = KS + KSS;
@@ -851,7 +970,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_kernel(const StatsArgs p) {
       for (int e = 0; e < PER; ++e) {
         const int x = tid + e * kNmThreads;
         const double zz = z[u][e];
-        z[u][e] = (iv && x < NO && zz > kGateZ) ? zz : 0.0;
+        z[u][e] = (iv && x < NO && zz > Gate<GM>::value) ? zz : 0.0;
       }
     }
 #pragma unroll
@@ -987,18 +1106,18 @@ bool plan_stats(StatsArgs &a, size_t &lds, int &ngroups) {
   return true;
 }
 
-template <int TPW>
+template <int TPW, int GM>
 static hipError_t launch_stats_t(const StatsArgs &a, int nchunk, int ngroups, size_t lds,
                                  hipStream_t st) {
-  hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(&stats_kernel<TPW>), lds);
+  hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(&stats_kernel<TPW, GM>), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((stats_kernel<TPW>), dim3(nchunk, ngroups), dim3(kStatsThreads), lds, st, a);
+  hipLaunchKernelGGL((stats_kernel<TPW, GM>), dim3(nchunk, ngroups), dim3(kStatsThreads), lds, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const int no = a.K * a.S + a.K * a.S * a.S;
   if (no <= 6 * kNmThreads)
-    hipLaunchKernelGGL((nm_kernel<6, 4>), dim3(nchunk), dim3(kNmThreads), 0, st, a);
+    hipLaunchKernelGGL((nm_kernel<6, 4, GM>), dim3(nchunk), dim3(kNmThreads), 0, st, a);
   else
-    hipLaunchKernelGGL((nm_kernel<24, 1>), dim3(nchunk), dim3(kNmThreads), 0, st, a);
+    hipLaunchKernelGGL((nm_kernel<24, 1, GM>), dim3(nchunk), dim3(kNmThreads), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1020,12 +1139,26 @@ static hipError_t launch_resp_k(const StatsArgs &a, int nchunk, size_t lds, hipS
   return hipGetLastError();
 }
 
+size_t vhem_resp_lds(int K, int KT) {
+  const size_t R = KT >= 1 && K % KT == 0 ? (size_t)(K / KT) : 1;
+  return std::max((size_t)(kRespThreads / 64) * ((size_t)K + R) * sizeof(double) +
+                      (size_t)K * sizeof(int),
+                  (size_t)(kRespThreads + 1) * sizeof(int));
+}
+
 hipError_t launch_resp(const StatsArgs &a, int nchunk, hipStream_t st) {
   // per-wave Nj accumulators of all K clusters in LDS (past 64 KB at K ~ 960: the
   // launch sets the dynamic-LDS attribute; the caller rejects K past a CU's LDS)
-  size_t lds = resp_lds(a.K, a.KT);
+  size_t lds = a.vhem ? vhem_resp_lds(a.K, a.KT) : resp_lds(a.K, a.KT);
   // the folded fallback borrows the accumulators' space first (queue + worker regions)
   if (a.fold) lds = std::max(lds, fold_lds_bytes(kRespThreads, kRespFoldWaves, a.fx.S, a.fx.SB));
+  if (a.vhem) {  // VHEM responsibilities and weights: one kernel for every K and trial count
+    if (a.KT < 1 || a.K % a.KT != 0 || !a.omegaB) return hipErrorInvalidValue;
+    hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(&vhem_resp_kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vhem_resp_kernel, dim3(nchunk), dim3(kRespThreads), lds, st, a);
+    return hipGetLastError();
+  }
   if (a.KT != a.K) {  // batched trials
     if (a.K > kRespSlots * 64 || a.KT < 1 || a.K % a.KT != 0) return hipErrorInvalidValue;
     hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(&resp_trials_kernel), lds);
@@ -1047,9 +1180,14 @@ hipError_t launch_stats(const StatsArgs &a, int nchunk, int ngroups, size_t lds,
   const int RG = a.JG * a.S;
   const int ntiles = ((RG + 15) / 16) * ((a.NU + 15) / 16);
   const int tpw = (ntiles + kStatsWaves - 1) / kStatsWaves;
-  if (tpw <= 4) return launch_stats_t<4>(a, nchunk, ngroups, lds, st);
-  if (tpw <= 8) return launch_stats_t<8>(a, nchunk, ngroups, lds, st);
-  return launch_stats_t<16>(a, nchunk, ngroups, lds, st);
+  if (a.vhem) {
+    if (tpw <= 4) return launch_stats_t<4, kGateVhem>(a, nchunk, ngroups, lds, st);
+    if (tpw <= 8) return launch_stats_t<8, kGateVhem>(a, nchunk, ngroups, lds, st);
+    return launch_stats_t<16, kGateVhem>(a, nchunk, ngroups, lds, st);
+  }
+  if (tpw <= 4) return launch_stats_t<4, kGateVbhem>(a, nchunk, ngroups, lds, st);
+  if (tpw <= 8) return launch_stats_t<8, kGateVbhem>(a, nchunk, ngroups, lds, st);
+  return launch_stats_t<16, kGateVbhem>(a, nchunk, ngroups, lds, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1589,9 +1727,10 @@ hipError_t launch_gate_list(const StatsArgs &a, int nchunk, hipStream_t st) {
   // the per-wave ballot masks grow with K: above 64 KB the launch needs the attribute
   // (the caller keeps the gated schedule only while this fits a CU, gate_list_lds)
   const size_t lds = gate_list_lds(a.K);
-  hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(&gate_list_kernel), lds);
+  auto *fn = a.vhem ? &gate_list_kernel<kGateVhem> : &gate_list_kernel<kGateVbhem>;
+  hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(fn), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(gate_list_kernel, dim3(nchunk), dim3(kListThreads), lds, st, a);
+  hipLaunchKernelGGL(fn, dim3(nchunk), dim3(kListThreads), lds, st, a);
   return hipGetLastError();
 }
 

@@ -208,6 +208,32 @@ class EStepEngine:
         _capi.check(fn(*args), name)
         return res
 
+    def fused_vhem(self, Ni: torch.Tensor, omegaB: torch.Tensor, inf_norm: float,
+                   smooth: float = 1.0, out: torch.Tensor = None) -> torch.Tensor:
+        """The VHEM fused E-step (vhem_estep_fused / _trials, honouring ``trials``).
+
+        Ni: [N] = Nv * omega_b * Kb, omegaB: [N] = omega_b (device, fp64); the cluster
+        constants are host.vhem_cluster_constants, ``set_log_omega`` takes log omega_r.
+        Returns the packed statistics ([stats_len]; ``unpack_stats`` layout with
+        LogL in the Lt1 slot); Z is left in ``self.hatZ``, the undivided L_elbo in
+        ``self.LL``."""
+        if self._ws_fused is None:
+            nb = int(self.lib.vhem_fused_trials_workspace_bytes(
+                ctypes.byref(self._bt), ctypes.byref(self._ct), self.trials, self.T))
+            self._ws_fused = torch.empty((max(nb, 1),), dtype=torch.uint8, device=self.device)
+        res = self.stats if out is None else out
+        sp = _capi.ptr(self.stats) if out is None else self._out_ptr(out)
+        head = (ctypes.byref(self._bt), ctypes.byref(self._ct))
+        head += (self.T,) if self.trials == 1 else (self.trials, self.T)
+        args = head + (float(smooth), _capi.ptr(Ni), _capi.ptr(omegaB), float(inf_norm),
+                       _capi.ptr(self.logOmega), sp, _capi.ptr(self.hatZ), _capi.ptr(self.LL),
+                       _capi.ptr(self._ws_fused), self._ws_fused.numel(), self._stream())
+        if self.trials == 1:
+            _capi.check(self.lib.vhem_estep_fused(*args), "vhem_estep_fused")
+        else:
+            _capi.check(self.lib.vhem_estep_fused_trials(*args), "vhem_estep_fused_trials")
+        return res
+
     def fallback_count(self) -> int:
         """Pairs of the last fused call that needed the exact fallback (syncs)."""
         ws = self._ws_fused if self._ws_fused is not None else self._ws_pairs

@@ -193,6 +193,44 @@ int vbhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *cl
                              double *stats_dev, double *hatZ_dev, double *LL_elbo_dev,
                              void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* VHEM mode of the fused E-step (hem_h3m_c_step.m:293-314, 430, 443 and the sums of
+ * hem_mstep_component.m:84-121) for one EM iteration of vhem_cluster:
+ *   clus: the vhem_estep_pairs descriptor (logA = log A_r, logPi = log prior_r, m,
+ *         P = inv Sigma_r or 1/sigma_r, c = log det Sigma_r); smooth: E /= smooth;
+ *   Ni_dev [N] = Nv * omega_b * Kb (:61), omegaB_dev [N] = omega_b, inf_norm the
+ *   scalar of :110-119, logOmega_dev [K] = log omega_r (-inf allowed: Z = 0 exactly).
+ * Per base i, cluster j: Ls = L_elbo / inf_norm, lz = logOmega[j] + Ni[i] * Ls (each
+ * operation rounded as written), Z = exp(lz - LSE_j lz) (no +1e-50), w = Z * omegaB[i],
+ * gate g = [w > 0] (hem_mstep_component.m:88).
+ * Outputs: Z_dev [N][K], LL_elbo_dev [N][K] (undivided L_elbo), and stats_dev in the
+ * layout and length of vbhem_estep_fused:
+ *   [ Nj = sum_i Z | N1 = sum g w nu_1 | M = sum g w sum_xi | LogL = sum_i LSE | 0 |
+ *     U = sum g w sum_b sum_t_nu u ]
+ * plain sums in a fixed order (bit-reproducible, summable across shards).  The trials
+ * form batches R trials as vbhem_estep_fused_trials does (logOmega_dev [R*KT], any
+ * R * KT the workspace fits; a trial's Z, Nj and LogL are bit-identical to the same
+ * trial run alone, and so are its other statistics while both calls split the gate
+ * lists into the same number of parts, min(chunks of bases, 4096 / (R * KT))); it
+ * needs the gated schedule.  The workspace is the VBHEM one: the
+ * *_workspace_bytes functions below return vbhem_fused_trials_workspace_bytes, and a
+ * workspace may be shared between VBHEM and VHEM calls of the same shape.  Schedules:
+ * vbhem_set_fused_mode (the gated one lists the pairs with w > 0; its backward-only
+ * pass runs on the kernel with the dense schedule's rounding of L_elbo, because
+ * Ni / inf_norm multiplies that rounding before the softmax). */
+size_t vhem_fused_workspace_bytes(const vbhem_base_t *base, const vbhem_cluster_t *clus, int T);
+size_t vhem_fused_trials_workspace_bytes(const vbhem_base_t *base, const vbhem_cluster_t *clus,
+                                         int R, int T);
+int vhem_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int T, double smooth,
+                     const double *Ni_dev, const double *omegaB_dev, double inf_norm,
+                     const double *logOmega_dev, double *stats_dev, double *Z_dev,
+                     double *LL_elbo_dev, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+int vhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
+                            double smooth, const double *Ni_dev, const double *omegaB_dev,
+                            double inf_norm, const double *logOmega_dev, double *stats_dev,
+                            double *Z_dev, double *LL_elbo_dev, void *workspace_dev,
+                            size_t workspace_bytes, void *stream);
+
 /* Host-array entry points of the fused E-step (what a MATLAB gateway binds; see
  * integration/vbhem_estep_fused_mex.c and INTEGRATION.md).
  *
