@@ -9,6 +9,7 @@ There is no CPU fallback: if the library is missing, :func:`lib` raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -121,6 +122,12 @@ EXPORTS = {
     "vbhem_timing_read_em_math": (_c_int, [ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_longlong)]),
     "vbhem_set_fused_mode": (_c_int, [_c_int]),
+    "vbhem_switch_count": (_c_int, []),
+    "vbhem_switch_name": (ctypes.c_char_p, [_c_int]),
+    "vbhem_switch_get": (_c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "vbhem_switch_set": (_c_int, [ctypes.c_char_p, ctypes.c_longlong,
+                                  ctypes.POINTER(ctypes.c_longlong)]),
+    "vbhem_switch_reset": (None, []),
     "vbhem_debug_extra_lds": (_c_size, [_c_size]),
     "vbhem_em_prelude": (_c_int, [ctypes.POINTER(PostT), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vbhem_em_lower_bound": (_c_int, [ctypes.POINTER(PostT), ctypes.POINTER(EmOptT), _vp, _vp,
@@ -242,3 +249,36 @@ FUSED_GATED, FUSED_DENSE = 0, 1
 def set_fused_mode(mode: int) -> int:
     """Fused E-step schedule (FUSED_GATED default, FUSED_DENSE); returns the previous one."""
     return int(lib().vbhem_set_fused_mode(int(mode)))
+
+
+def switch_names() -> list:
+    """The library's run-time switches ("VBHEM_NO_BWD4", ...)."""
+    return [lib().vbhem_switch_name(i).decode() for i in range(lib().vbhem_switch_count())]
+
+
+def get_switch(name: str) -> int:
+    v = ctypes.c_longlong()
+    check(lib().vbhem_switch_get(name.encode(), ctypes.byref(v)), "vbhem_switch_get")
+    return v.value
+
+
+def set_switch(name: str, value: int) -> int:
+    """Set a switch (with or without the VBHEM_ prefix) for this thread; returns the
+    previous value."""
+    prev = ctypes.c_longlong()
+    check(lib().vbhem_switch_set(name.encode(), int(value), ctypes.byref(prev)), "vbhem_switch_set")
+    return prev.value
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """``with switches(NO_BWD4=1, GROUP_BASES=64): ...`` -- this thread's switches set
+    inside the block, the previous values back on exit (also after an exception)."""
+    prev = []
+    try:
+        for name, value in values.items():
+            prev.append((name, set_switch(name, value)))
+        yield
+    finally:
+        for name, value in reversed(prev):
+            set_switch(name, value)

@@ -62,13 +62,46 @@ std::string split_name(const vbhem::SplitArgs &a) {
          std::to_string(a.mode) + ">";
 }
 
-// fused schedule of this host thread (vbhem_set_fused_mode; VBHEM_FUSED_DENSE=1
-// in the environment sets every thread's default)
-int default_fused_mode() {
-  const char *ev = std::getenv("VBHEM_FUSED_DENSE");
-  return (ev && std::atoi(ev) != 0) ? VBHEM_FUSED_DENSE : VBHEM_FUSED_GATED;
+// The switch table (vbhem_switches.h) by index, for the vbhem_switch_* functions
+struct SwitchRow {
+  const char *name;  // with the VBHEM_ prefix, as in the environment
+  long long unset;
+  long long vbhem::Switches::*field;
+};
+constexpr SwitchRow kSwitchRows[] = {
+#define X(name, unset, doc) {"VBHEM_" #name, unset, &vbhem::Switches::name},
+    VBHEM_SWITCHES(X)
+#undef X
+};
+constexpr int kSwitchCount = (int)(sizeof(kSwitchRows) / sizeof(kSwitchRows[0]));
+
+// a boolean switch holds 0 or 1; an integer one any value (negative: not set)
+long long switch_value(const SwitchRow &r, long long v) { return r.unset == 0 ? (v != 0) : v; }
+
+// the process default: the environment, read once (the library's only getenv)
+const vbhem::Switches &default_switches() {
+  static const vbhem::Switches def = [] {
+    vbhem::Switches s;
+    for (const SwitchRow &r : kSwitchRows)
+      if (const char *ev = std::getenv(r.name)) {
+        if (r.unset == 0) s.*r.field = ev[0] != '\0' && std::strcmp(ev, "0") != 0;
+        else s.*r.field = std::strtoll(ev, nullptr, 10);
+      }
+    return s;
+  }();
+  return def;
 }
-thread_local int g_fused_mode = default_fused_mode();
+// the set of this host thread (the fused schedule, vbhem_set_fused_mode, is its
+// FUSED_DENSE entry)
+thread_local vbhem::Switches g_switches = default_switches();
+
+const SwitchRow *find_switch(const char *name) {
+  if (!name) return nullptr;
+  if (std::strncmp(name, "VBHEM_", 6) == 0) name += 6;
+  for (const SwitchRow &r : kSwitchRows)
+    if (std::strcmp(name, r.name + 6) == 0) return &r;
+  return nullptr;
+}
 
 // timing is recorded for this launch: enabled on this thread and the stream
 // is not capturing
@@ -101,6 +134,7 @@ void timing_recycle(hipEvent_t ev) {
 
 // EM-loop math kernel timing (vbhem_em.hip), same events and levels as the E-step's
 namespace vbhem {
+const Switches &switches() { return g_switches; }
 void *timing_begin(hipStream_t st) { return timing_on(st) ? timing_event(st) : nullptr; }
 void timing_end_em_math(void *ev0, hipStream_t st) {
   if (ev0) g_timing.emd.emplace_back(static_cast<hipEvent_t>(ev0), timing_event(st));
@@ -339,7 +373,7 @@ struct Carver {
 // emission_u_kernel applies (k-steps <= kUMaxKq): the per-call operand U is needed
 // unless the caller prepared one (base->U)
 bool u_gemm_ok(const vbhem_base_t *b) {
-  return vbhem::emission_kdp(b->d, b->covmode) / 4 <= vbhem::kUMaxKq && !std::getenv("VBHEM_NO_UGEMM");
+  return vbhem::emission_kdp(b->d, b->covmode) / 4 <= vbhem::kUMaxKq && !vbhem::switches().NO_UGEMM;
 }
 bool need_u_ws(const vbhem_base_t *b) { return !b->U && u_gemm_ok(b); }
 
@@ -394,11 +428,12 @@ size_t carve_fused(void *ws, const vbhem_base_t *b, const vbhem_cluster_t *c, in
   const size_t per_base = (size_t)K * (S + (size_t)S * S + 2 * (size_t)S * SB) * sizeof(double);
   size_t g = std::max<size_t>(1, kGroupBudget / std::max<size_t>(1, per_base));
   g = std::min<size_t>(g, (size_t)std::max(1, b->N));
-  if (const char *ev = std::getenv("VBHEM_GROUP_BASES"))  // tests: force several groups
-    g = std::max<size_t>(1, std::min<size_t>(g, (size_t)std::atoll(ev)));
+  const vbhem::Switches &sw = vbhem::switches();
+  if (sw.GROUP_BASES >= 0)  // tests: force several groups
+    g = std::max<size_t>(1, std::min<size_t>(g, (size_t)sw.GROUP_BASES));
   w.group = (int)g;
   int maxslab = kMaxSlabs;
-  if (const char *ev = std::getenv("VBHEM_NSLAB")) maxslab = std::max(1, std::min(8192, std::atoi(ev)));
+  if (sw.NSLAB >= 0) maxslab = (int)std::max(1ll, std::min(8192ll, sw.NSLAB));
   w.nslab = std::min<int>(w.group, maxslab);
   w.slab_len = R * (int)vbhem_stats_len(K / R, S, b->d, b->covmode);
   // flagged-pair list: with the fallback folded into the consumers the backward pass's
@@ -495,19 +530,19 @@ int prepare_fb(FbCtx &c, const vbhem_base_t *b, const vbhem_cluster_t *cl, int T
     al.prior = b->prior; al.A = b->A; al.logA = cl->logA; al.logPi = cl->logPi;
     vbhem::SplitArgs &ab = c.bwd.a;
     ab.prior = b->prior; ab.A = b->A; ab.logA = cl->logA; ab.logPi = cl->logPi;
-    if (c.bwd.ok && cl->S <= vbhem::kBwd2MaxS && !std::getenv("VBHEM_NO_BWD2")) {
+    if (c.bwd.ok && cl->S <= vbhem::kBwd2MaxS && !vbhem::switches().NO_BWD2) {
       if (!split_first_pass) {
         c.bwd2_nwb = vbhem::bwd2_waves(cl->S);
         c.bwd2_lds = vbhem::bwd2_lds(cl->S, c.bwd2_nwb);
         c.bwd2_ppb = vbhem::bwd2_ppb(cl->S, c.bwd2_nwb);
-        c.bwd4 = vbhem::bwd4_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD4");
-        c.bwd12 = vbhem::bwd12_supported(cl->S, b->SB) && !std::getenv("VBHEM_NO_BWD12");
+        c.bwd4 = vbhem::bwd4_supported(cl->S, b->SB) && !vbhem::switches().NO_BWD4;
+        c.bwd12 = vbhem::bwd12_supported(cl->S, b->SB) && !vbhem::switches().NO_BWD12;
       }
-      c.list4 = vbhem::list4_supported(cl->S, b->SB, T, cl->K) && !std::getenv("VBHEM_NO_LIST4");
-      c.list12 = vbhem::list12_supported(cl->S, b->SB, T, cl->K) && !std::getenv("VBHEM_NO_LIST12");
+      c.list4 = vbhem::list4_supported(cl->S, b->SB, T, cl->K) && !vbhem::switches().NO_LIST4;
+      c.list12 = vbhem::list12_supported(cl->S, b->SB, T, cl->K) && !vbhem::switches().NO_LIST12;
     }
     c.k1_in_kernel = c.use_u && c.bwd2_lds && !c.bwd4 && !c.bwd12 && !c.list4 && !c.list12 &&
-                     c.em.kdp <= vbhem::kK1InKernelMaxKdp && !std::getenv("VBHEM_NO_K1_IN_KERNEL");
+                     c.em.kdp <= vbhem::kK1InKernelMaxKdp && !vbhem::switches().NO_K1_IN_KERNEL;
   }
   return VBHEM_OK;
 }
@@ -569,7 +604,7 @@ int run_fb_list(const FbCtx &c, int i_begin, int i_end, int i_buf0, double *nu1,
   // persistent grid has a scratch slot per wavefront (then no launch after the pass)
   ca.xinline = 0;
   auto set_inline = [&](long long waves) {
-    if (!fold || waves > kExactThreads || std::getenv("VBHEM_NO_LIST_INLINE")) return;
+    if (!fold || waves > kExactThreads || vbhem::switches().NO_LIST_INLINE) return;
     ca.xinline = 1;
     ca.xscr = scratch;
     ca.xstride = (long long)exact_stride(c.plan.a.S, c.plan.a.SB, c.plan.a.T);
@@ -1009,7 +1044,8 @@ static int fused_impl(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
   // gated schedule: split kernel + list statistics tile must apply
   size_t sl_lds = 0;
   // (gate lists: per-wave ballot masks of all K clusters in LDS, K up to ~2,400)
-  const bool gated = g_fused_mode == VBHEM_FUSED_GATED && ctx.split.ok && ctx.split.lds_l &&
+  const vbhem::Switches &sw = vbhem::switches();  // this thread's set, fixed for the call
+  const bool gated = !sw.FUSED_DENSE && ctx.split.ok && ctx.split.lds_l &&
                      vbhem::plan_stats_list(sa, sl_lds) &&
                      vbhem::gate_list_lds(K) <= kLdsLimit;
   if (R > 1 && !gated)
@@ -1051,7 +1087,7 @@ static int fused_impl(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
   // (thread 448 of the block runs the flag-head handshake: blocks of >= 8 waves only;
   // smaller ones, e.g. a VBHEM_BWD2_WAVES build, take the emission_prep_kernel path)
   if (gated && ctx.k1_in_kernel && ctx.em.zfix && ctx.bwd2_nwb * 64 >= 512 &&
-      !std::getenv("VBHEM_NO_BWD2_PREP")) {
+      !sw.NO_BWD2_PREP) {
     ctx.em.W = w.W; ctx.em.bias = w.bias; ctx.em.shift = w.shift;
     ctx.bwd2_prep = true;
     ctx.fpre = w.fpre;
@@ -1065,7 +1101,7 @@ static int fused_impl(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
   // their launch in launch_stats_list, from flag_count[3]); resp_kernel needs a
   // scratch slot per chunk block: at most kExactThreads chunks
   const bool fold = gated && R == 1 && base->N <= w.group && ctx.split.ok && K < kExactThreads &&
-                    w.nslab <= kExactThreads && !std::getenv("VBHEM_NO_FOLD_EXACT");
+                    w.nslab <= kExactThreads && !sw.NO_FOLD_EXACT;
   sa.fold = 0;
   for (int g0 = 0; g0 < base->N; g0 += w.group) {
     const int g1 = std::min(base->N, g0 + w.group);
@@ -1162,10 +1198,34 @@ int vhem_estep_fused_trials(const vbhem_base_t *base, const vbhem_cluster_t *clu
 }
 
 int vbhem_set_fused_mode(int mode) {
-  const int prev = g_fused_mode;
-  if (mode == VBHEM_FUSED_GATED || mode == VBHEM_FUSED_DENSE) g_fused_mode = mode;
+  const int prev = g_switches.FUSED_DENSE ? VBHEM_FUSED_DENSE : VBHEM_FUSED_GATED;
+  if (mode == VBHEM_FUSED_GATED || mode == VBHEM_FUSED_DENSE)
+    g_switches.FUSED_DENSE = mode == VBHEM_FUSED_DENSE;
   return prev;
 }
+
+int vbhem_switch_count(void) { return kSwitchCount; }
+
+const char *vbhem_switch_name(int index) {
+  return index >= 0 && index < kSwitchCount ? kSwitchRows[index].name : nullptr;
+}
+
+int vbhem_switch_get(const char *name, long long *value) {
+  const SwitchRow *r = find_switch(name);
+  if (!r) return fail(VBHEM_ERR_ARG, std::string("unknown switch: ") + (name ? name : "(null)"));
+  if (value) *value = g_switches.*r->field;
+  return VBHEM_OK;
+}
+
+int vbhem_switch_set(const char *name, long long value, long long *previous) {
+  const SwitchRow *r = find_switch(name);
+  if (!r) return fail(VBHEM_ERR_ARG, std::string("unknown switch: ") + (name ? name : "(null)"));
+  if (previous) *previous = g_switches.*r->field;
+  g_switches.*r->field = switch_value(*r, value);
+  return VBHEM_OK;
+}
+
+void vbhem_switch_reset(void) { g_switches = default_switches(); }
 
 int vbhem_timing_enable(int on) {
   g_timing.level = (on == 1 || on == 2) ? on : 0;

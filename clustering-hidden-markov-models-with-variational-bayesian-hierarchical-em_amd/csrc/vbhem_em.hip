@@ -714,7 +714,7 @@ int vbhem_em_run_ext(const vbhem_base_t *base, const double *tildeN_dev, int T,
   const size_t need = vbhem_em_workspace_bytes(base, K, S, T);
   if (need == 0 || !workspace_dev || workspace_bytes < need) return VBHEM_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!vbhem::em_dev_supported(d, S) || std::getenv("VBHEM_EM_HOST_MATH"))
+  if (!vbhem::em_dev_supported(d, S) || vbhem::switches().EM_HOST_MATH)
     return em_run_host(base, tildeN_dev, T, opt, post, LogLs, iters, L_final, stable, stats_dev,
                        hatZ_dev, LL_dev, workspace_dev, st, allreduce, allreduce_ctx, ext);
   vbhem_cluster_t c0 = {K, S, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -999,7 +999,7 @@ static hipError_t launch_u_fn(const EmissionArgs &a, size_t lds, hipStream_t st)
   if (SPL != 1 && !PF) return hipErrorInvalidValue;
   if (BST && !PF) return hipErrorInvalidValue;
   if constexpr (PF && !BST)
-    if (em_bst_ok(a) && !std::getenv("VBHEM_EM_NOBST"))  // (A/B switch)
+    if (em_bst_ok(a) && !switches().EM_NOBST)  // (A/B switch)
       return launch_u_fn<KQB, RC, NTW, EXACT, PF, SPL, true>(a, lds, st);
   auto *fn = &emission_u_kernel<KQB, RC, NTW, EXACT, PF, SPL, BST>;
   hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(fn), lds);
@@ -1075,7 +1075,7 @@ static hipError_t launch_raw_kq(const EmissionArgs &a, size_t lds, hipStream_t s
 // device's waves (the last, partial round then costs a smaller share); above that the
 // doubled U reads cost more than the finer tail saves.  VBHEM_EM_SPLIT=0 / 1 forces it.
 static bool use_row_split(const EmissionArgs &a) {
-  if (const char *ev = std::getenv("VBHEM_EM_SPLIT")) return std::atoi(ev) != 0;
+  if (switches().EM_SPLIT >= 0) return switches().EM_SPLIT != 0;
   const long long ntile = ((long long)(a.i_end - a.i_begin) * a.SB + 15) / 16;
   const long long waves = (long long)device_cus() * 3 * a.nwave;  // 3 blocks per CU
   return ntile < 4 * waves;
@@ -1086,7 +1086,7 @@ hipError_t launch_emission(const EmissionArgs &a, size_t lds, hipStream_t st) {
   if (ncols <= 0) return hipSuccess;
   if (a.U && a.urc) {
     // W' in one chunk (K S <= 128): the double-buffered variant
-    const bool one = a.ksp / 16 == a.urc && !std::getenv("VBHEM_NO_UPF");
+    const bool one = a.ksp / 16 == a.urc;
     if (a.ukqb == 4) return one ? launch_u_fn<4, 8, 1, false, true>(a, lds, st) : launch_u_fn<4, 8, 1>(a, lds, st);
     if (a.ukqb == 12) {
       if (one && use_row_split(a))  // small base counts (shards): half-tiles, a finer last round
@@ -1097,7 +1097,7 @@ hipError_t launch_emission(const EmissionArgs &a, size_t lds, hipStream_t st) {
     if (a.kdp / 4 == 38) {  // d = 16 full (C5)
       // double-buffered chunks with buffer stores (E below 4 GB; VBHEM_EM_NODB: A/B)
       // (emission_db_kernel has no E /= smooth: the VHEM calls take emission_u_kernel)
-      if (a.smooth == 1.0 && em_bst_ok(a) && (a.ksp / 16) % 4 == 0 && !std::getenv("VBHEM_EM_NODB"))
+      if (a.smooth == 1.0 && em_bst_ok(a) && (a.ksp / 16) % 4 == 0 && !switches().EM_NODB)
         return launch_db_fn<38, 2, 2>(a, st);
       return launch_u_fn<38, 4, UNTW, true>(a, lds, st);
     }

@@ -9,6 +9,8 @@
 #include <string>
 #include <tuple>
 
+#include "vbhem_switches.h"  // struct Switches, switches()
+
 namespace vbhem {
 
 // record `msg` for vbhem_last_error() and return `code` (vbhem_capi.hip)

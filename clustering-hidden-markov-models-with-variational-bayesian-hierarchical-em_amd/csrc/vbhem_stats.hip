@@ -1166,7 +1166,7 @@ hipError_t launch_resp(const StatsArgs &a, int nchunk, hipStream_t st) {
     hipLaunchKernelGGL(resp_trials_kernel, dim3(nchunk), dim3(kRespThreads), lds, st, a);
     return hipGetLastError();
   }
-  switch (std::getenv("VBHEM_RESP_GENERIC") ? 0 : a.K) {  // (A/B: the generic kernel)
+  switch (switches().RESP_GENERIC ? 0 : a.K) {  // (A/B: the generic kernel)
     case 4: return launch_resp_k<4>(a, nchunk, lds, st);
     case 8: return launch_resp_k<8>(a, nchunk, lds, st);
     case 16: return launch_resp_k<16>(a, nchunk, lds, st);
@@ -1777,7 +1777,7 @@ static hipError_t launch_sm_pd(const StatsArgs &a, const dim3 &grid, hipStream_t
   // at most the slab count per cluster (grid.x is the cap from launch_stats_list)
   long long nb = (long long)resident_per_cu(reinterpret_cast<const void *>(fn), 64 * kSmWaves, lds) *
                  device_cus();
-  if (const char *ev = std::getenv("VBHEM_SU_BLOCKS")) nb = std::atoll(ev);  // A/B
+  if (switches().SU_BLOCKS >= 0) nb = switches().SU_BLOCKS;  // A/B
   nb = std::min<long long>(std::max<long long>(nb, a.K + 1), grid.x);
   hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(64 * kSmWaves), lds, st, a);
   return hipGetLastError();
@@ -1838,7 +1838,7 @@ static hipError_t launch_sg(const StatsArgs &a, const dim3 &grid, hipStream_t st
 
 // lanes per pair group for the grouped kernel (0: shape too large for it)
 static int sg_lanes(const StatsArgs &a) {
-  if (std::getenv("VBHEM_NO_STATS_G")) return 0;
+  if (switches().NO_STATS_G) return 0;
   const int OT = a.S * a.SB, nu4 = a.ukdp * a.SB;
   for (int LG : {8, 16, 32})
     if (a.NU <= LG && OT <= 4 * LG && a.S * a.S <= 4 * LG && nu4 <= 8 * LG) return LG;
@@ -1866,7 +1866,8 @@ hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStre
   if (stats_slabs) *stats_slabs = nchunk;
   const int NO = a.S + a.S * a.S + a.S * a.NU;
   const dim3 grid(nchunk, a.K);
-  const bool no_u = std::getenv("VBHEM_NO_STATS_U") != nullptr;
+  const Switches &sw = switches();
+  const bool no_u = sw.NO_STATS_U;
   // blocks of the list kernels on the prepared operand: the per-block cost (wave
   // reduction, slab writes) grows with the output count NO: at most ~4M block outputs
   // per launch (C4: 512 x 16 blocks of 432, C5: 64 x 32 of 1992 -- measured: 16384
@@ -1876,8 +1877,7 @@ hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStre
   const long long NOb = (long long)a.S + (long long)a.S * a.S + (long long)a.S * a.NU;
   long long cap = (4ll << 20) / (NOb * std::max(1, a.K));
   cap = std::min<long long>(cap, 4096 / std::max(1, a.K));
-  if (const char *ev = std::getenv("VBHEM_SU_BLOCKS"))  // A/B
-    cap = std::atoi(ev) / std::max(1, a.K);
+  if (sw.SU_BLOCKS >= 0) cap = sw.SU_BLOCKS / std::max(1, a.K);  // A/B
   const int nb = (int)std::max(1ll, std::min((long long)nchunk, cap));
   const dim3 g2(nb, a.K);
   StatsArgs b = a;
@@ -1899,7 +1899,7 @@ hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStre
   // below 2^32 -- always so for a workspace group, checked anyway)
   const bool z32 = (unsigned long long)(a.i_end - a.i_buf0) * (unsigned long long)a.K < (1ull << 32);
   if (a.Us && !no_u && z32 && a.S <= 16 && a.SB <= 16 && us_nup(a.NU) <= 12 * 16 &&
-      !std::getenv("VBHEM_NO_STATS_M")) {
+      !sw.NO_STATS_M) {
     // one 1-D grid over all clusters' gated pairs (balanced parts; the block maps
     // itself to (cluster, part)); at most nzero_m parts per cluster, so the slabs past
     // them hold none of its N1 / M / U entries (stats_final_kernel reads only those)
@@ -1917,11 +1917,11 @@ hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStre
   // kernel's range) (NU > 64, e.g. d = 16 full at C5: the covariance gather of
   // stats_list_kernel measured 2 % faster, 1.74 vs 1.78 ms per 100 k-base step;
   // VBHEM_STATS_U=1 forces it)
-  const bool su = a.NU <= 64 || std::getenv("VBHEM_STATS_U");
+  const bool su = a.NU <= 64 || sw.STATS_U;
   if (a.U && su && a.S <= 16 && a.SB <= a.S && a.NU <= 3 * 64 && !no_u) {
     // the grouped kernel runs 64 / LG pairs per wave at once: half the blocks (C3,
     // 80 per cluster: statistics 0.047 -> 0.043 ms; with 156 it was 0.057)
-    const dim3 gg(std::getenv("VBHEM_SU_BLOCKS") ? nb : std::max(1, nb / 2), a.K);
+    const dim3 gg(sw.SU_BLOCKS >= 0 ? nb : std::max(1, nb / 2), a.K);
     switch (lg) {
       case 8: return launch_sg_s<8>(b, gg, st);
       case 16: return launch_sg_s<16>(b, gg, st);

@@ -86,9 +86,9 @@ size_t vbhem_em_workspace_bytes(const vbhem_base_t *base, int K, int S, int T);
  * on the device (vbhem_em_dev.hip) and the loop keeps the next iteration queued
  * while it reads this one's bound (one iteration ahead: a converging run computes
  * one E-step it then discards, so stats_dev holds the statistics of the last E-step
- * RUN); otherwise, or with VBHEM_EM_HOST_MATH set, the host math runs in C++ on the
- * host between synchronous E-steps.  The all-reduce callback always reduces
- * stats_dev, once per E-step run, in the same order on every rank. */
+ * RUN); otherwise, or with the switch VBHEM_EM_HOST_MATH on (vbhem_switch_set), the
+ * host math runs in C++ on the host between synchronous E-steps.  The all-reduce
+ * callback always reduces stats_dev, once per E-step run, in the same order on every rank. */
 int vbhem_em_run(const vbhem_base_t *base, const double *tildeN_dev, int T,
                  const vbhem_em_opt_t *opt, vbhem_post_t *post, double *LogLs, int *iters,
                  double *L_final, int *stable, double *stats_dev, double *hatZ_dev,

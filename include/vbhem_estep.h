@@ -256,8 +256,9 @@ int vbhem_estep_fused_host(int device, const vbhem_base_t *base_host,
                            const double *logOmega_host, double *stats_host, double *hatZ_host,
                            double *LL_elbo_host);
 
-/* Fused E-step schedule of the calling host thread (default VBHEM_FUSED_GATED,
- * or VBHEM_FUSED_DENSE=1 in the environment).  Both give the same outputs:
+/* Fused E-step schedule of the calling host thread (default VBHEM_FUSED_GATED; it is
+ * the switch VBHEM_FUSED_DENSE below, so VBHEM_FUSED_DENSE=1 in the environment makes
+ * the dense schedule every thread's default).  Both give the same outputs:
  *   VBHEM_FUSED_GATED  backward sweep + log-likelihood for every pair, then the
  *                      forward sweep and statistics only for the pairs the gate
  *                      Z > 1e-8 of vbhem_compute_Statistics.m:35 keeps (the
@@ -267,6 +268,18 @@ int vbhem_estep_fused_host(int device, const vbhem_base_t *base_host,
 #define VBHEM_FUSED_GATED 0
 #define VBHEM_FUSED_DENSE 1
 int vbhem_set_fused_mode(int mode);
+
+/* Run-time switches (A/B runs and tests; none is needed in production).
+ * The process defaults are the VBHEM_* environment variables, read once; every host
+ * thread starts from them and changes only its own set.  A boolean switch is on (1)
+ * when its variable is set to anything but "0" or ""; an integer switch holds the
+ * variable's value, negative when not set.  Names are accepted with or without the
+ * VBHEM_ prefix; an unknown name: VBHEM_ERR_ARG, vbhem_last_error() gives the name. */
+int vbhem_switch_count(void);
+const char *vbhem_switch_name(int index); /* "VBHEM_NO_BWD4", ...; NULL past the end */
+int vbhem_switch_get(const char *name, long long *value);
+int vbhem_switch_set(const char *name, long long value, long long *previous); /* this thread */
+void vbhem_switch_reset(void); /* this thread back to the environment's defaults */
 
 /* Number of pairs the last call on this thread had to recompute with the
  * exact (reference-order, Theta-storing) fallback because the factorised

@@ -1,5 +1,5 @@
 """MFMA-kernel A/B check on the GPU: L_elbo of fb_bwd4_kernel against
-fb_bwd2_kernel (VBHEM_NO_BWD4=1, read when each call plans its kernels) and the
+fb_bwd2_kernel (the switch VBHEM_NO_BWD4) and the
 statistics of fb_list4_kernel against fb_split_kernel's list mode (VBHEM_NO_LIST4=1)
 on a C4 workload; prints the largest relative difference and where the mismatches sit
 (base index mod 16, cluster).  Development tool.
@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import pkgload  # noqa: E402
 
 vb = pkgload.load()
+from vbhem_amd import _capi  # noqa: E402
 from vbhem_amd.estep import EStepEngine  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
@@ -25,17 +26,12 @@ eng.set_clusters(consts)
 eng.set_log_omega(vb.host.log_omega_tilde(post.alpha))
 tN = (float(opt["Nv"]) * N) * eng.base.omega
 out, st = {}, {}
-for mode, env in (("mfma", {}), ("split", {"VBHEM_NO_LIST4": "1"}),
-                  ("bwd2", {"VBHEM_NO_BWD4": "1", "VBHEM_NO_LIST4": "1"})):
-    for k in ("VBHEM_NO_BWD4", "VBHEM_NO_LIST4"):
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    s = eng.fused(tN).cpu().numpy().copy()
+for mode, sw in (("mfma", {}), ("split", {"NO_LIST4": 1}), ("bwd2", {"NO_BWD4": 1, "NO_LIST4": 1})):
+    with _capi.switches(**sw):
+        s = eng.fused(tN).cpu().numpy().copy()
     torch.cuda.synchronize()
     out[mode] = eng.LL.cpu().numpy().copy()
     st[mode] = s
-for k in ("VBHEM_NO_BWD4", "VBHEM_NO_LIST4"):
-    os.environ.pop(k, None)
 for m in ("mfma", "split"):
     d = np.abs(st[m] - st["bwd2"]) / np.maximum(np.abs(st["bwd2"]), 1e-300)
     big = np.abs(st["bwd2"]) > 1e-12 * np.abs(st["bwd2"]).max()

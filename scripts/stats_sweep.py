@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """A/B of the gated-statistics kernels in one process: the fused E-step on a config
-under several environment settings (read per launch by vbhem_stats.hip), statistics
-time per step from the library's event timing.
+under several switch settings (_capi.switches), statistics time per step from the
+library's event timing.
 
-    python scripts/stats_sweep.py [--config C4] [--N n] ENV=VAL,ENV=VAL ...   ('-' = defaults)
+    python scripts/stats_sweep.py [--config C4] [--N n] SWITCH=VAL,SWITCH=VAL ...   ('-' = defaults)
 """
 import argparse
 import json
@@ -35,31 +35,27 @@ def main():
     eng.set_clusters(consts)
     eng.set_log_omega(host.log_omega_tilde(post.alpha))
     ref = None
-    keys = set()
     for rnd in range(2):  # two rounds: the second shows the spread
         for st in args.settings:
             env = {} if st == "-" else dict(kv.split("=") for kv in st.split(","))
-            keys |= set(env)
-            for k in keys:
-                os.environ.pop(k, None)
-            os.environ.update(env)
-            out = eng.fused(tN).clone()
-            torch.cuda.synchronize()
-            if ref is None:
-                ref = out
-            err = float(((out - ref).abs() / ref.abs().clamp_min(1e-30)).max())
-            t0 = time.perf_counter()
-            for _ in range(args.reps):
-                eng.fused(tN)
-            torch.cuda.synchronize()
-            step_ms = (time.perf_counter() - t0) * 1e3 / args.reps
-            _capi.timing_read()
-            _capi.timing_enable(True)
-            for _ in range(args.reps):
-                eng.fused(tN)
-            torch.cuda.synchronize()
-            _capi.timing_enable(False)
-            t = _capi.timing_read()
+            with _capi.switches(**env):
+                out = eng.fused(tN).clone()
+                torch.cuda.synchronize()
+                if ref is None:
+                    ref = out
+                err = float(((out - ref).abs() / ref.abs().clamp_min(1e-30)).max())
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    eng.fused(tN)
+                torch.cuda.synchronize()
+                step_ms = (time.perf_counter() - t0) * 1e3 / args.reps
+                _capi.timing_read()
+                _capi.timing_enable(True)
+                for _ in range(args.reps):
+                    eng.fused(tN)
+                torch.cuda.synchronize()
+                _capi.timing_enable(False)
+                t = _capi.timing_read()
             print(json.dumps(dict(round=rnd, setting=st, step_ms=step_ms, stats_ms=t["stats_ms"] / args.reps,
                                   fb_ms=t["fb_ms"] / args.reps, max_rel_vs_first=err)), flush=True)
 

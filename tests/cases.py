@@ -8,12 +8,25 @@ would leave logA constant and hide indexing errors).
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
+import pytest
 
 import pkgload
 import vbhem_oracle as vo
 
 vb = pkgload.load()
+
+
+@pytest.fixture
+def lib_switches():
+    """``lib_switches(NO_BWD4=1)`` enters ``_capi.switches(...)`` for the rest of the
+    test (this thread's library switches; names with or without the VBHEM_ prefix).
+    Test modules import it from here."""
+    from vbhem_amd import _capi
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(_capi.switches(**values))
 
 
 def post_dict(post) -> dict:

@@ -8,8 +8,6 @@ one and several W' row chunks (K*S <= 128 and > 128), ragged bases, face-scale
 means (the fixed base-mean shift of the prepared operand), and the per-call operand
 (prepare=False: built for each call's bases, shifted by the cluster means).
 """
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -35,18 +33,15 @@ SHAPES = {
 
 
 def _pairs(vb, cs, prepare, old=False):
+    from vbhem_amd import _capi
     from vbhem_amd.estep import EStepEngine
-    if old:
-        os.environ["VBHEM_NO_UGEMM"] = "1"
-    try:
+    with _capi.switches(NO_UGEMM=old):
         K, S = cs["consts"]["logPi"].shape
         eng = EStepEngine(cs["bs"], K, S, cs["T"], device=DEV, prepare=prepare)
         eng.set_clusters(cs["consts"])
         out = eng.pairs(want_tnu=True)
         torch.cuda.synchronize()
         return {k: v.cpu().numpy() for k, v in out.items()}, eng
-    finally:
-        os.environ.pop("VBHEM_NO_UGEMM", None)
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -130,18 +125,17 @@ def test_prepared_operand_layout(vb):
 
 @pytest.mark.parametrize("name", ["full_d8", "full_d16", "diag_d12", "full_d2_face", "full_d4_long"])
 @pytest.mark.parametrize("prepare", [True, False])
-def test_stats_on_prepared_operand(vb, name, prepare, monkeypatch):
+def test_stats_on_prepared_operand(vb, name, prepare):
     """Gated statistics from the prepared operand (stats_list_u_kernel, and
     stats_list_g_kernel for small NU: moments read from U and shifted back by z) vs the
     covariance gather (stats_list_kernel), with several
     base groups (the second group adds into the slabs) and fewer blocks than chunks (the
     first group zero-fills the slabs past its grid)."""
-    from vbhem_amd import host
+    from vbhem_amd import _capi, host
     from vbhem_amd.estep import EStepEngine
     N, K, S, Sb, d, cov, extra = SHAPES[name]
     N = max(N, 40)
     cs = make_case(N, K, S, Sb, d, cov, seed=11 + len(name), **extra)
-    monkeypatch.setenv("VBHEM_GROUP_BASES", str(N // 2 + 1))
     outs = []
     # VBHEM_STATS_U=1: the prepared-operand kernel also where the default picks the
     # covariance path (NU > 64)
@@ -155,15 +149,11 @@ def test_stats_on_prepared_operand(vb, name, prepare, monkeypatch):
                 {"VBHEM_STATS_U": "1", "VBHEM_SU_BLOCKS": str(K), **no_m},
                 {"VBHEM_STATS_U": "1", "VBHEM_NO_STATS_G": "1", **no_m},
                 {}, {"VBHEM_SU_BLOCKS": str(K + 1)}):
-        for k in ("VBHEM_NO_STATS_U", "VBHEM_SU_BLOCKS", "VBHEM_STATS_U", "VBHEM_NO_STATS_G",
-                  "VBHEM_NO_STATS_M"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        eng = EStepEngine(cs["bs"], K, S, cs["T"], device=DEV, prepare=prepare)
-        eng.set_clusters(cs["consts"])
-        eng.set_log_omega(host.log_omega_tilde(cs["P"].alpha))
-        st = eng.fused((100.0 * N) * eng.base.omega).cpu().numpy()
+        with _capi.switches(GROUP_BASES=N // 2 + 1, **env):
+            eng = EStepEngine(cs["bs"], K, S, cs["T"], device=DEV, prepare=prepare)
+            eng.set_clusters(cs["consts"])
+            eng.set_log_omega(host.log_omega_tilde(cs["P"].alpha))
+            st = eng.fused((100.0 * N) * eng.base.omega).cpu().numpy()
         outs.append(st)
     assert np.isfinite(outs[0]).all()
     for st in outs[1:]:
@@ -171,23 +161,23 @@ def test_stats_on_prepared_operand(vb, name, prepare, monkeypatch):
 
 
 @pytest.mark.parametrize("N", [37, 2001, 12500])
-def test_row_split_bit_identical(vb, monkeypatch, N):
+def test_row_split_bit_identical(vb, N):
     """The one-chunk GEMM in half-tiles (small base counts, e.g. a 12,500-base shard:
     each wave takes 4 of a tile's 8 row tiles) computes every E entry with the same MFMA
     chain as the whole-tile kernel: the fused E-step's outputs are bit-identical with the
     split forced on and off (VBHEM_EM_SPLIT), at C4's shape."""
-    from vbhem_amd import host
+    from vbhem_amd import _capi, host
     from vbhem_amd.estep import EStepEngine
     base, P, opt = vb.synth_workload("C4", N=N, device=DEV)
     consts = host.cluster_constants(P, base.covmode)
     outs = []
-    for split in ("0", "1"):
-        monkeypatch.setenv("VBHEM_EM_SPLIT", split)
-        eng = EStepEngine(base, P.K, P.S, opt["tau"], device=DEV)
-        eng.set_clusters(consts)
-        eng.set_log_omega(host.log_omega_tilde(P.alpha))
-        tN = (100.0 * N) * eng.base.omega
-        outs.append((eng.fused(tN).clone(), eng.LL.clone(), eng.hatZ.clone()))
+    for split in (0, 1):
+        with _capi.switches(EM_SPLIT=split):
+            eng = EStepEngine(base, P.K, P.S, opt["tau"], device=DEV)
+            eng.set_clusters(consts)
+            eng.set_log_omega(host.log_omega_tilde(P.alpha))
+            tN = (100.0 * N) * eng.base.omega
+            outs.append((eng.fused(tN).clone(), eng.LL.clone(), eng.hatZ.clone()))
         del eng
     for a, b in zip(*outs):
         assert torch.equal(a, b)
@@ -196,27 +186,24 @@ def test_row_split_bit_identical(vb, monkeypatch, N):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg,N", [("C4", 12500), ("C3", 4000)])
 @pytest.mark.parametrize("switch", ["VBHEM_EM_NOBST", "VBHEM_RESP_GENERIC"])
-def test_store_paths_bit_identical(vb, monkeypatch, cfg, N, switch):
+def test_store_paths_bit_identical(vb, cfg, N, switch):
     """The one-chunk emission GEMM's buffer stores (lanes outside the tile dropped by an
     out-of-range offset) and resp_kernel's K-templated path (unrolled group reductions,
     buffer stores of hat_Z / Z) write exactly what the branched paths write: the fused
-    E-step's outputs are bit-identical with VBHEM_EM_NOBST / VBHEM_RESP_GENERIC set and
-    unset (both read at launch), C4's shape (K = 16) and C3's (K = 8)."""
-    from vbhem_amd import host
+    E-step's outputs are bit-identical with VBHEM_EM_NOBST / VBHEM_RESP_GENERIC on and
+    off, C4's shape (K = 16) and C3's (K = 8)."""
+    from vbhem_amd import _capi, host
     from vbhem_amd.estep import EStepEngine
     base, P, opt = vb.synth_workload(cfg, N=N, device=DEV)
     consts = host.cluster_constants(P, base.covmode)
     outs = []
     for on in (False, True):
-        if on:
-            monkeypatch.setenv(switch, "1")
-        else:
-            monkeypatch.delenv(switch, raising=False)
-        eng = EStepEngine(base, P.K, P.S, opt["tau"], device=DEV)
-        eng.set_clusters(consts)
-        eng.set_log_omega(host.log_omega_tilde(P.alpha))
-        tN = (100.0 * N) * eng.base.omega
-        outs.append((eng.fused(tN).clone(), eng.LL.clone(), eng.hatZ.clone()))
+        with _capi.switches(**{switch: on}):
+            eng = EStepEngine(base, P.K, P.S, opt["tau"], device=DEV)
+            eng.set_clusters(consts)
+            eng.set_log_omega(host.log_omega_tilde(P.alpha))
+            tN = (100.0 * N) * eng.base.omega
+            outs.append((eng.fused(tN).clone(), eng.LL.clone(), eng.hatZ.clone()))
         del eng
     for a, b in zip(*outs):
         assert torch.equal(a, b)

@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-from cases import SHAPES, make_case
+from cases import SHAPES, lib_switches, make_case  # noqa: F401  (lib_switches: a fixture)
 from conftest import RTOL_NORTH_STAR, RTOL_PAIRS, elem_err, hatz_err, post_err, rel_err, stat_err
 
 pytestmark = pytest.mark.gpu
@@ -102,12 +102,11 @@ def test_fused_matches_oracle(vb, vo, shape, mode_tscale):
     assert elem_err(eng.LL.cpu().numpy(), pairs["LL_elbo"]) < RTOL_PAIRS
 
 
-def test_fused_multigroup(vb, vo, fused_mode, monkeypatch):
+def test_fused_multigroup(vb, vo, fused_mode, lib_switches):
     """The fused call split into several base groups (VBHEM_GROUP_BASES: E, the
     per-pair scratch and the gate lists are per group; the slabs accumulate)."""
     name, N, K, S, Sb, d, cov, T = "multigroup", 300, 6, 5, 4, 3, 1, 7
-    monkeypatch.setenv("VBHEM_GROUP_BASES", "64")
-    monkeypatch.setenv("VBHEM_NSLAB", "7")
+    lib_switches(GROUP_BASES=64, NSLAB=7)
     cs = make_case(N, K, S, Sb, d, cov, seed=seed_of(name), ragged=True, tau=T)
     base, consts = cs["base"], cs["consts"]
     pairs = vo.c_estep_pairs(base, consts, T, nthreads=4)
@@ -124,7 +123,7 @@ def test_fused_multigroup(vb, vo, fused_mode, monkeypatch):
 
 
 @pytest.mark.parametrize("S,Sb,d,cov", [(5, 5, 2, 0), (3, 3, 2, 1), (6, 4, 4, 0)])
-def test_k1_in_recursion_kernels(vb, vo, S, Sb, d, cov, monkeypatch):
+def test_k1_in_recursion_kernels(vb, vo, S, Sb, d, cov):
     """Gated schedule with a short K1 (kdp <= 8: d = 2 full, d <= 4 diag -- C2, C3):
     fb_bwd2_kernel and fb_split_kernel's list mode evaluate E from the prepared
     operand, with no emission GEMM and no E buffer.  Statistics, hat_Z and L_elbo
@@ -142,11 +141,10 @@ def test_k1_in_recursion_kernels(vb, vo, S, Sb, d, cov, monkeypatch):
         st = vo.c_statistics(Z, pairs, cov)
         out = {}
         for label in ("in_kernel", "gemm"):
-            if label == "gemm":
-                monkeypatch.setenv("VBHEM_NO_K1_IN_KERNEL", "1")
-            eng = engine(vb, base, consts, T)
-            eng.set_log_omega(logOmega)
-            raw = eng.fused(torch.as_tensor(tN, device=DEV)).cpu().numpy()
+            with _capi.switches(NO_K1_IN_KERNEL=label == "gemm"):
+                eng = engine(vb, base, consts, T)
+                eng.set_log_omega(logOmega)
+                raw = eng.fused(torch.as_tensor(tN, device=DEV)).cpu().numpy()
             out[label] = (vb.host.unpack_stats(raw, K, S, d, cov), eng.LL.cpu().numpy(),
                           eng.hatZ.cpu().numpy())
             del eng
@@ -165,7 +163,7 @@ def test_k1_in_recursion_kernels(vb, vo, S, Sb, d, cov, monkeypatch):
     (5, 5, 2, 0, False, 333, None), (3, 3, 2, 1, False, 333, None), (4, 4, 1, 1, False, 333, None),
     (6, 4, 4, 0, False, 333, None), (4, 4, 2, 1, True, 333, None), (5, 3, 2, 0, True, 333, None),
     (5, 5, 2, 0, False, 40000, None), (5, 5, 2, 0, True, 5000, None), (5, 5, 2, 0, False, 5000, 1200)])
-def test_bwd2_in_kernel_prep(vb, vo, S, Sb, d, cov, adv, N, group, monkeypatch):
+def test_bwd2_in_kernel_prep(vb, vo, S, Sb, d, cov, adv, N, group, lib_switches):
     """emission_prep_kernel's work inside fb_bwd2_kernel (SplitArgs::prep: the short-K1
     gated schedule on a prepared operand, C2 / C3): W', bias', A' computed per block with
     the same arithmetic, the fallback counters zeroed in the kernel unless the previous
@@ -177,7 +175,7 @@ def test_bwd2_in_kernel_prep(vb, vo, S, Sb, d, cov, adv, N, group, monkeypatch):
     for every base (both passes flag it; the exact fallback runs inside the steps)."""
     from vbhem_amd import _capi
     if group:
-        monkeypatch.setenv("VBHEM_GROUP_BASES", str(group))
+        lib_switches(GROUP_BASES=group)
     prev = _capi.set_fused_mode(_capi.FUSED_GATED)
     try:
         K, T = 4, 6 if adv else 10
@@ -197,18 +195,16 @@ def test_bwd2_in_kernel_prep(vb, vo, S, Sb, d, cov, adv, N, group, monkeypatch):
             return (eng.stats.cpu().numpy().copy(), eng.LL.cpu().numpy().copy(),
                     eng.hatZ.cpu().numpy().copy(), eng.fallback_count())
 
-        monkeypatch.setenv("VBHEM_NO_BWD2_PREP", "1")
-        e0 = engine(vb, base, consts, T)
-        e0.set_log_omega(logOmega)
-        ref = run(e0)
-        del e0
-        monkeypatch.delenv("VBHEM_NO_BWD2_PREP")
+        with _capi.switches(NO_BWD2_PREP=1):
+            e0 = engine(vb, base, consts, T)
+            e0.set_log_omega(logOmega)
+            ref = run(e0)
+            del e0
         eng = engine(vb, base, consts, T)
         eng.set_log_omega(logOmega)
         outs = [run(eng), run(eng)]
-        monkeypatch.setenv("VBHEM_NO_BWD2_PREP", "1")
-        outs.append(run(eng))  # the launch path: its head zeroed, tag included
-        monkeypatch.delenv("VBHEM_NO_BWD2_PREP")
+        with _capi.switches(NO_BWD2_PREP=1):
+            outs.append(run(eng))  # the launch path: its head zeroed, tag included
         outs.append(run(eng))
         head = eng._ws_fused.view(torch.int32)
         head[:2] = 0               # the tag cleared ...
@@ -258,12 +254,11 @@ def test_exact_fallback_pairs(vb, vo, cov):
 
 
 @pytest.mark.parametrize("env", [{}, {"VBHEM_NO_FOLD_EXACT": "1"}])
-def test_exact_fallback_large_states(vb, vo, env, monkeypatch):
+def test_exact_fallback_large_states(vb, vo, env, lib_switches):
     """S = 20, Sb = 18: a flagged pair's small arrays (6 S Sb + S^2 + Sb doubles) no
     longer fit the wavefront's LDS region, so exact_pair_wave keeps them in the tail of
     its global scratch slot (agent-scope fences between its exchange steps)."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    lib_switches(**env)
     cs, consts = adversarial_case(1, S=20, Sb=18, d=3, N=6, K=2, T=5)
     consts["c"][1:] = 1.0e4
     base, T = cs["base"], cs["T"]
@@ -303,7 +298,7 @@ def test_exact_fallback_fused(vb, vo, fused_mode):
 @pytest.mark.parametrize("N,K", [(4, 1), (300, 2), (3000, 2)])
 @pytest.mark.parametrize("env", [{}, {"VBHEM_NO_FOLD_EXACT": "1"}, {"VBHEM_NO_STATS_M": "1"},
                                  {"VBHEM_NO_LIST_INLINE": "1"}])
-def test_exact_fallback_gated_pairs(vb, vo, N, K, env, monkeypatch):
+def test_exact_fallback_gated_pairs(vb, vo, N, K, env, lib_switches):
     """The adversarial cluster wins every base (the other cluster's emissions are far
     worse), so its pairs are flagged by the backward pass AND are gated: the gate-list
     pass flags them again.  Default: the backward pass's fallback folded into resp_kernel
@@ -311,8 +306,7 @@ def test_exact_fallback_gated_pairs(vb, vo, N, K, env, monkeypatch):
     (fb_split_kernel, S = 4: SplitArgs::xinline); VBHEM_NO_LIST_INLINE: an fb_exact_kernel
     launch for the list pass's instead; VBHEM_NO_FOLD_EXACT: a launch after each pass;
     VBHEM_NO_STATS_M: the other statistics kernels."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    lib_switches(**env)
     cs, consts = adversarial_case(1, N=N, K=K)
     if K > 1:
         consts["c"][1:] = 1.0e4
@@ -334,15 +328,14 @@ def test_exact_fallback_gated_pairs(vb, vo, N, K, env, monkeypatch):
 
 @pytest.mark.parametrize("env", [{}, {"VBHEM_NO_FOLD_EXACT": "1"}, {"VBHEM_NO_LIST_INLINE": "1"}])
 @pytest.mark.parametrize("S,N", [(8, 41), (8, 5000), (12, 41)])
-def test_exact_fallback_mfma_kernels(vb, vo, env, monkeypatch, S, N):
+def test_exact_fallback_mfma_kernels(vb, vo, env, lib_switches, S, N):
     """The adversarial cluster at S = Sb = 8 (12), T = 10: its pairs underflow in the
     MFMA backward pass (fb_bwd4_kernel / fb_bwd12_kernel) and, being gated, again in
     the gate-list pass (fb_list4_kernel / fb_list12_kernel); both passes' flags reach
     the exact fallback (folded into the consumers -- fb_list4_kernel's from its per-wave
     queue; at N = 5000 waves hold two items, 8 queued pairs -- or fb_exact_kernel
     launches)."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    lib_switches(**env)
     K = 2
     cs, consts = adversarial_case(1, S=S, Sb=S, d=3, N=N, K=K, T=10)
     consts["c"][1:] = 1.0e4
@@ -403,7 +396,7 @@ def _emission(base, consts):
 @pytest.mark.parametrize("env", [{}, {"VBHEM_NO_FOLD_EXACT": "1"}])
 @pytest.mark.parametrize("case", ["near", "far", "rowsum", "far+rowsum"])
 @pytest.mark.parametrize("S", [8, 12])
-def test_range_check_exact_flags(vb, vo, S, case, env, monkeypatch):
+def test_range_check_exact_flags(vb, vo, S, case, env, lib_switches):
     """The per-tile range check of the MFMA kernels flags exactly the pairs it must
     (ADVICE r05): one base state of one base pushed towards or out of range -- its E
     column made very negative through that state's covariance (every cluster shares one
@@ -413,8 +406,7 @@ def test_range_check_exact_flags(vb, vo, S, case, env, monkeypatch):
     past it, so the backward pass flags the base's K pairs and the gate-list pass its
     gated ones again; "rowsum" flags the row's base in both passes.  The fallback count
     must equal that exactly, and every output must be the oracle's."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    lib_switches(**env)
     N, K, d, T = 41, 3, 3, 10
     cs = make_case(N, K, S, S, d, 1, seed=9, tau=T)
     base = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in cs["base"].items()}

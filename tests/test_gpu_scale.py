@@ -196,14 +196,15 @@ def test_c4_full_size_vs_oracle(vb, vo):
 
 
 @pytest.mark.gpu
-def test_c5_multigroup_vs_oracle(vb, vo, monkeypatch):
+def test_c5_multigroup_vs_oracle(vb, vo):
     """C5 shapes (K = 32, S = Sb = 12, d = 16 full) on 20,000 bases (640,000 pairs)
     through the multi-group path of the full-size run: VBHEM_GROUP_BASES = 6,000
     splits the call into 4 base groups (C5 at N = 10^6 runs as 14 groups of
     <= 74 k), each with its own emission GEMM, backward pass, gate lists and list
     statistics accumulated into the same slabs."""
-    monkeypatch.setenv("VBHEM_GROUP_BASES", "6000")
-    assert _full_size_vs_oracle(vb, vo, "C5", N=20_000, chunk=1000) == 20_000
+    from vbhem_amd import _capi
+    with _capi.switches(GROUP_BASES=6000):
+        assert _full_size_vs_oracle(vb, vo, "C5", N=20_000, chunk=1000) == 20_000
 
 
 @pytest.mark.gpu

@@ -196,13 +196,13 @@ def test_native_em_rccl_one_rank(vb):
 
 
 @pytest.mark.gpu
-def test_native_em_unstable_device_path(vb, monkeypatch):
+def test_native_em_unstable_device_path(vb):
     """A NaN bound on the device EM path (the next iteration already queued): the
     run stops unstable with L = -inf, the posterior is the one before the failing
     iteration's M-step, and hat_Z is that iteration's -- as the host-math path
     (VBHEM_EM_HOST_MATH) gives."""
     import torch
-    from vbhem_amd import native_em
+    from vbhem_amd import _capi, native_em
     from vbhem_amd.estep import EStepEngine
     cs = make_case(200, 3, 3, 3, 2, 1, seed=35, tau=6)
     P = cs["P"].copy()
@@ -211,8 +211,8 @@ def test_native_em_unstable_device_path(vb, monkeypatch):
     eng = EStepEngine(cs["bs"], 3, 3, 6, device="cuda:0")
     dev = native_em.run(P, eng, opt, calc_deriv=True)
     hz_dev = dev.hatZ.clone()
-    monkeypatch.setenv("VBHEM_EM_HOST_MATH", "1")
-    host = native_em.run(P, eng, opt, calc_deriv=True)
+    with _capi.switches(EM_HOST_MATH=1):
+        host = native_em.run(P, eng, opt, calc_deriv=True)
     for r in (dev, host):
         assert not r.stable and r.LL == -np.inf and r.iters == 0 and r.LogLs == []
         assert all(np.isnan(np.atleast_1d(v)).all() for v in r.dLL.values())

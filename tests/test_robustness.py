@@ -159,20 +159,14 @@ def test_fused_into_pinned_host_memory(vb, trials):
     directly (no device-to-host copy); bit-identical to the device vector, also
     with several base groups (the first group writes, later ones add) and on
     repeat calls into the same buffer."""
-    import os
-    from vbhem_amd import host
+    from vbhem_amd import _capi, host
     cs = make_case(500, 4, 5, 5, 3, 1, seed=43, tau=8)
     c0 = cs["consts"]
     consts = c0 if trials == 1 else {k: np.concatenate([np.asarray(c0[k])] * trials) for k in c0}
     logOm = host.log_omega_tilde(cs["P"].alpha)
     tN = _tn(cs)
-    old = os.environ.get("VBHEM_GROUP_BASES")
-    for group in (None, "128"):
-        if group is None:
-            os.environ.pop("VBHEM_GROUP_BASES", None)
-        else:
-            os.environ["VBHEM_GROUP_BASES"] = group
-        try:
+    for group in (-1, 128):  # -1: not set (one group)
+        with _capi.switches(GROUP_BASES=group):
             eng = _engine(vb, cs, trials=trials, consts=consts)
             eng.set_log_omega(np.concatenate([logOm] * trials))
             ref = eng.fused(tN).clone()
@@ -188,11 +182,6 @@ def test_fused_into_pinned_host_memory(vb, trials):
             eng.fused(tN, out=other)
             torch.cuda.synchronize()
             assert torch.equal(other, ref.cpu())
-        finally:
-            if old is None:
-                os.environ.pop("VBHEM_GROUP_BASES", None)
-            else:
-                os.environ["VBHEM_GROUP_BASES"] = old
     with pytest.raises(Exception):
         eng.fused(tN, out=torch.zeros(eng.stats_len, dtype=torch.float64))  # pageable memory
 
