@@ -171,6 +171,13 @@ EXPORTS = {
                                    _c_size, _vp]),
     "vbhmm_ppk_gram": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(ScoreHmmsT), _vp,
                                 _c_int, _c_int, _vp, _vp]),
+    "vbhmm_ccfd_distance_workspace_bytes": (_c_size, [_c_int, ctypes.c_longlong]),
+    "vbhmm_ccfd_distance": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT), _vp, _vp,
+                                     _c_size, _vp, _vp, _vp, _vp]),
+    "vbhmm_ccfd_rowstats": (_c_int, [_vp, _c_int, _vp, _vp, _vp]),
+    "vbhmm_ccfd_rho": (_c_int, [_vp, _c_int, ctypes.POINTER(ctypes.c_double), _c_int, _vp, _vp]),
+    "vbhmm_ccfd_delta": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _vp, _vp, _vp]),
+    "vbhmm_ccfd_border": (_c_int, [_vp, _c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),
