@@ -5,11 +5,11 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function
 LIBDIR   := $(PKG)/lib
-SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_stats.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip
-HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h
+SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_stats.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_dic.hip
+HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h
 OBJS     := $(patsubst $(PKG)/csrc/%.hip,$(LIBDIR)/%.o,$(SRCS))
 
-all: lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck
+all: lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck
 
 lib: $(LIBDIR)/libvbhem_estep.so
 
@@ -59,8 +59,15 @@ ccfdcheck: tests/ccfdcheck/libccfdcheck.so
 tests/ccfdcheck/libccfdcheck.so: tests/ccfdcheck/ccfdcheck.hip $(PKG)/csrc/vbhmm_ccfd_row.h $(PKG)/csrc/vbhmm_score_pair.h include/vbhmm_ccfd.h include/vbhmm_score.h include/vbhmm_fb.h include/vbhem_estep.h $(LIBDIR)/libvbhem_estep.so
 	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(PKG)/csrc -shared -o $@ $< -L$(LIBDIR) -lvbhem_estep -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
+# test-only: the pair routine of vbhmm_dic_pair.h on the host, and the library's DIC
+# likelihood kernels behind the same call
+diccheck: tests/diccheck/libdiccheck.so
+
+tests/diccheck/libdiccheck.so: tests/diccheck/diccheck.hip $(PKG)/csrc/vbhmm_dic_pair.h $(PKG)/csrc/vbhem_math.h include/vbhmm_dic.h include/vbhem_estep.h $(LIBDIR)/libvbhem_estep.so
+	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(PKG)/csrc -shared -o $@ $< -L$(LIBDIR) -lvbhem_estep -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
 clean:
-	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so tests/mathcheck/libmathcheck.so tests/scorecheck/libscorecheck.so tests/ppkcheck/libppkcheck.so tests/ccfdcheck/libccfdcheck.so
+	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so tests/mathcheck/libmathcheck.so tests/scorecheck/libscorecheck.so tests/ppkcheck/libppkcheck.so tests/ccfdcheck/libccfdcheck.so tests/diccheck/libdiccheck.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck clean
+.PHONY: all lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck clean

@@ -62,6 +62,13 @@ class ScoreHmmsT(ctypes.Structure):  # include/vbhmm_score.h vbhmm_score_hmms_t
                 ("nstates", _vp), ("prior", _vp), ("trans", _vp), ("mean", _vp), ("cov", _vp)]
 
 
+class DicModelsT(ctypes.Structure):  # include/vbhmm_dic.h vbhmm_dic_models_t
+    _fields_ = [("G", _c_int), ("C", _c_int), ("S", _c_int), ("d", _c_int),
+                ("max_model_clusters", _c_int), ("model_off", _vp), ("nstates_r", _vp),
+                ("logw", _vp), ("scale", _vp), ("logA", _vp), ("logPi", _vp), ("m", _vp),
+                ("P", _vp), ("c", _vp)]
+
+
 class EmExtT(ctypes.Structure):  # include/vbhem_em.h vbhem_em_ext_t
     _fields_ = [("rccl_comm", _vp), ("iter_seconds", _vp), ("calc_deriv", _c_int), ("dLL", _vp)]
 
@@ -178,6 +185,9 @@ EXPORTS = {
     "vbhmm_ccfd_rho": (_c_int, [_vp, _c_int, ctypes.POINTER(ctypes.c_double), _c_int, _vp, _vp]),
     "vbhmm_ccfd_delta": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _vp, _vp, _vp]),
     "vbhmm_ccfd_border": (_c_int, [_vp, _c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "vbhmm_dic_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int]),
+    "vbhmm_dic_loglik": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int, _vp, _vp,
+                                  _vp, _c_size, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),
