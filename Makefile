@@ -5,11 +5,11 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function
 LIBDIR   := $(PKG)/lib
-SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_stats.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_dic.hip
-HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h
+SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_stats.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_dic.hip $(PKG)/csrc/vbhmm_em.hip
+HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h include/vbhmm_em.h $(PKG)/csrc/vbhmm_em_run.h
 OBJS     := $(patsubst $(PKG)/csrc/%.hip,$(LIBDIR)/%.o,$(SRCS))
 
-all: lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck
+all: lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck vbhmmemcheck
 
 lib: $(LIBDIR)/libvbhem_estep.so
 
@@ -66,8 +66,21 @@ diccheck: tests/diccheck/libdiccheck.so
 tests/diccheck/libdiccheck.so: tests/diccheck/diccheck.hip $(PKG)/csrc/vbhmm_dic_pair.h $(PKG)/csrc/vbhem_math.h include/vbhmm_dic.h include/vbhem_estep.h $(LIBDIR)/libvbhem_estep.so
 	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(PKG)/csrc -shared -o $@ $< -L$(LIBDIR) -lvbhem_estep -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
+# test-only: the serial walker over the run routines of vbhmm_em_run.h on the host, and the
+# library's batched EM kernels behind the same call
+vbhmmemcheck: tests/vbhmmemcheck/libvbhmmemcheck.so
+
+tests/vbhmmemcheck/libvbhmmemcheck.so: tests/vbhmmemcheck/vbhmmemcheck.hip $(PKG)/csrc/vbhmm_em_run.h include/vbhmm_em.h include/vbhmm_fb.h include/vbhem_estep.h $(LIBDIR)/libvbhem_estep.so
+	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(PKG)/csrc -shared -o $@ $< -L$(LIBDIR) -lvbhem_estep -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+# test-only, CPU: the serial walker in a stand-alone program under the address and
+# undefined-behaviour sanitizers (not part of `all`, not run by pytest)
+vbhmmem_sanitize: tests/vbhmmemcheck/walker_main.cpp $(PKG)/csrc/vbhmm_em_run.h
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(PKG)/csrc -o tests/vbhmmemcheck/walker_sanitize $<
+	tests/vbhmmemcheck/walker_sanitize
+
 clean:
-	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so tests/mathcheck/libmathcheck.so tests/scorecheck/libscorecheck.so tests/ppkcheck/libppkcheck.so tests/ccfdcheck/libccfdcheck.so tests/diccheck/libdiccheck.so
+	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so tests/mathcheck/libmathcheck.so tests/scorecheck/libscorecheck.so tests/ppkcheck/libppkcheck.so tests/ccfdcheck/libccfdcheck.so tests/diccheck/libdiccheck.so tests/vbhmmemcheck/libvbhmmemcheck.so tests/vbhmmemcheck/walker_sanitize
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck clean
+.PHONY: all lib oracle mex mathcheck scorecheck ppkcheck ccfdcheck diccheck vbhmmemcheck vbhmmem_sanitize clean

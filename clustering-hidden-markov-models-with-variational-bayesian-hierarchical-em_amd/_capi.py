@@ -57,6 +57,25 @@ class HmmParamsT(ctypes.Structure):  # include/vbhmm_fb.h vbhmm_params_t
                 ("const_denominator", ctypes.c_double)]
 
 
+class EmSubjectsT(ctypes.Structure):  # include/vbhmm_em.h vbhmm_em_subjects_t
+    _fields_ = [("seqs", SeqsT), ("S", _c_int), ("seq_first", _vp), ("max_seqs", _c_int),
+                ("max_obs", _c_int)]
+
+
+class EmRunsT(ctypes.Structure):  # include/vbhmm_em.h vbhmm_em_runs_t
+    _fields_ = [("R", _c_int), ("KM", _c_int), ("subject", _vp), ("K", _vp), ("post", _vp)]
+
+
+class EmHyperT(ctypes.Structure):  # include/vbhmm_em.h vbhmm_em_hyper_t
+    _fields_ = [("alpha0", ctypes.c_double), ("epsilon0", ctypes.c_double),
+                ("beta0", ctypes.c_double), ("v0", ctypes.c_double),
+                ("m0", ctypes.c_double * 8), ("W0inv_diag", ctypes.c_double * 8)]
+
+
+class EmBatchOptT(ctypes.Structure):  # include/vbhmm_em.h vbhmm_em_opt_t
+    _fields_ = [("max_iter", _c_int), ("min_diff", ctypes.c_double), ("chunk_runs", _c_int)]
+
+
 class ScoreHmmsT(ctypes.Structure):  # include/vbhmm_score.h vbhmm_score_hmms_t
     _fields_ = [("H", _c_int), ("KM", _c_int), ("dim", _c_int), ("covmode", _c_int),
                 ("nstates", _vp), ("prior", _vp), ("trans", _vp), ("mean", _vp), ("cov", _vp)]
@@ -188,6 +207,14 @@ EXPORTS = {
     "vbhmm_dic_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int]),
     "vbhmm_dic_loglik": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int, _vp, _vp,
                                   _vp, _c_size, _vp]),
+    "vbhmm_em_post_len": (_c_size, [_c_int, _c_int]),
+    "vbhmm_em_stats_len": (_c_size, [_c_int, _c_int]),
+    "vbhmm_em_batch_workspace_bytes": (_c_size, [ctypes.POINTER(EmSubjectsT), _c_int, _c_int, _c_int]),
+    "vbhmm_em_batch": (_c_int, [ctypes.POINTER(EmSubjectsT), ctypes.POINTER(EmRunsT),
+                                ctypes.POINTER(EmHyperT), ctypes.POINTER(EmBatchOptT), _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "vbhmm_em_gamma": (_c_int, [ctypes.POINTER(EmSubjectsT), ctypes.POINTER(EmRunsT), _vp, _vp, _vp,
+                                _c_int, _vp, _c_size, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),

@@ -61,6 +61,36 @@ class SequenceBatch:
         return _capi.SeqsT(self.N, self.dim, self.maxT, _capi.ptr(self.offsets), _capi.ptr(self.x))
 
 
+class SubjectBatch:
+    """The sequences of several subjects resident on the GPU for the batched EM
+    (include/vbhmm_em.h): one packed :class:`SequenceBatch` of every subject's
+    sequences in subject order, seq_first [S+1] (subject s owns sequences
+    seq_first[s] .. seq_first[s+1]-1), and per subject the host copy X [obs][dim]
+    of its observations (what vbhmm_init reads)."""
+
+    def __init__(self, datas, dim: int, device="cuda"):
+        self.dim = int(dim)
+        self.datas = [[np.asarray(a, dtype=np.float64).reshape(-1, dim) for a in d] for d in datas]
+        self.S = len(self.datas)
+        if self.S < 1:
+            raise ValueError("SubjectBatch needs at least one subject")
+        self.seqs = SequenceBatch([a for d in self.datas for a in d], dim, device)
+        self.device = self.seqs.device
+        first = np.zeros(self.S + 1, dtype=np.int32)
+        first[1:] = np.cumsum([len(d) for d in self.datas])
+        self.lens = [np.array([a.shape[0] for a in d], dtype=np.int64) for d in self.datas]
+        self.obs = np.array([int(l.sum()) for l in self.lens], dtype=np.int64)
+        self.X = [np.concatenate(d, axis=0) if len(d) else np.zeros((0, dim)) for d in self.datas]
+        self.max_seqs = int(max(len(d) for d in self.datas))
+        self.max_obs = int(self.obs.max())
+        self.seq_first_host = first
+        self.seq_first = torch.from_numpy(first).to(self.device)
+
+    def desc(self) -> "_capi.EmSubjectsT":
+        return _capi.EmSubjectsT(self.seqs.desc(), self.S, _capi.ptr(self.seq_first), self.max_seqs,
+                                 self.max_obs)
+
+
 def vbhmm_fb(data, varpar: dict, device="cuda", pre: Optional[dict] = None,
              batch: Optional[SequenceBatch] = None) -> dict:
     """fbstats of vbhmm_fb.m for the sequences ``data`` (list of [T_n x dim]

@@ -236,6 +236,27 @@ def vbhmm_em_lb(st: dict, opt: dict, vp: dict, fb: dict, do_deriv: bool = False,
     LB = float(Lt1 + Lt2 + Lt3 + Lt4 + Lt5 - Lt6 - Lt7 - Lt8)
     if not do_deriv:
         return LB
+    return LB, vbhmm_em_lb_derivs(st, opt, vp, fb, clipped)
+
+
+def vbhmm_em_lb_derivs(st: dict, opt: dict, vp: dict, pre: dict, clipped: Optional[dict] = None) -> dict:
+    """vbhmm_em_lb.m:260-400: the bound's derivatives with respect to the (transformed)
+    hyperparameters at the posterior ``vp``.  They need the posterior and its prelude
+    alone (``pre``: logLambdaTilde, logPiTilde, logATilde), no statistics: ``st`` gives
+    dim, K, W0inv and W0mode.  The batched EM calls this on the posterior it kept from
+    the last E-step."""
+    dim, K = st["dim"], st["K"]
+    alpha0, epsilon0, beta0, v0 = opt["alpha0"], opt["epsilon0"], opt["beta0"], opt["v0"]
+    m0, W0inv = opt["mu0"], st["W0inv"]
+    v, W, m, beta = vp["v"], vp["W"], vp["m"], vp["beta"]
+    lLT, lPi, lA = pre["logLambdaTilde"], pre["logPiTilde"], pre["logATilde"]
+    logdetW0inv = (dim * np.log(W0inv[0, 0]) if st["W0mode"] == "iid"
+                   else np.log(np.diag(W0inv)).sum())
+    q = np.arange(1, dim + 1)
+    mWm = np.zeros(K)
+    for k in range(K):
+        dm = m[k] - m0
+        mWm[k] = dm @ W[k] @ dm
     # vbhmm_em_lb.m:263-320: the partial derivatives of Lt3 (alpha0), Lt4 (epsilon0)
     # and Lt5 (v0, beta0, W0, m0) -- the only terms holding hyperparameters
     d = {}
@@ -268,7 +289,7 @@ def vbhmm_em_lb(st: dict, opt: dict, vp: dict, fb: dict, do_deriv: bool = False,
                d_logbeta0=d["beta0"] * beta0, d_sqrtbeta0=d["beta0"] * 2 * np.sqrt(beta0),
                d_sqrtW0inv=d["W0"] * (myW0 ** 1.5) * (-2), d_logW0=d["W0"] * myW0,
                d_m0=np.asarray(d["m0"], dtype=np.float64))
-    return LB, dLB
+    return dLB
 
 
 # ----------------------------------------------------------------------------
@@ -368,6 +389,254 @@ def vbhmm_em(data: Sequence[np.ndarray], K: int, opt: dict, gmm: Optional[dict] 
 
 
 # ----------------------------------------------------------------------------
+# batched EM: every run of a list in one fused call (include/vbhmm_em.h)
+# ----------------------------------------------------------------------------
+FUSED_MAX_K, FUSED_MAX_DIM = 8, 8
+EM_STATUS = ("converged", "max_iter", "unstable", "bad_run")
+
+
+def em_post_len(KM: int, dim: int) -> int:
+    return KM * (3 + KM + dim + dim * dim)
+
+
+def em_stats_len(KM: int, dim: int) -> int:
+    return KM * (2 + KM + dim + dim * dim)
+
+
+def pack_posterior(vp: dict, K: int, KM: int, dim: int) -> np.ndarray:
+    """A posterior as include/vbhmm_em.h packs it: [alpha KM | epsilon KM x KM | beta KM |
+    v KM | m KM x dim | W KM x dim x dim], states and epsilon rows padded to KM (alpha,
+    epsilon, beta, v with 1, W with I: values no run reads)."""
+    al, be, v = np.ones(KM), np.ones(KM), np.ones(KM)
+    eps, m = np.ones((KM, KM)), np.zeros((KM, dim))
+    W = np.repeat(np.eye(dim)[None], KM, axis=0)
+    al[:K], be[:K], v[:K] = np.reshape(vp["alpha"], -1), np.reshape(vp["beta"], -1), np.reshape(vp["v"], -1)
+    eps[:K, :K], m[:K], W[:K] = vp["epsilon"], vp["m"], vp["W"]
+    return np.concatenate([al, eps.ravel(), be, v, m.ravel(), W.ravel()])
+
+
+def unpack_posterior(vec: np.ndarray, K: int, KM: int, dim: int) -> dict:
+    o = np.cumsum([0, KM, KM * KM, KM, KM, KM * dim, KM * dim * dim])
+    part = [np.asarray(vec[o[i]:o[i + 1]], dtype=np.float64) for i in range(6)]
+    return dict(alpha=part[0][:K].copy(), epsilon=part[1].reshape(KM, KM)[:K, :K].copy(),
+                beta=part[2][:K].copy(), v=part[3][:K].copy(), m=part[4].reshape(KM, dim)[:K].copy(),
+                W=part[5].reshape(KM, dim, dim)[:K].copy())
+
+
+def unpack_stats(vec: np.ndarray, K: int, KM: int, dim: int) -> dict:
+    o = np.cumsum([0, KM, KM, KM * KM, KM * dim, KM * dim * dim])
+    part = [np.asarray(vec[o[i]:o[i + 1]], dtype=np.float64) for i in range(5)]
+    return dict(Nk1=part[0][:K].copy(), Nk=part[1][:K].copy(), M=part[2].reshape(KM, KM)[:K, :K].copy(),
+                xbar=part[3].reshape(KM, dim)[:K].copy(), t1_S=part[4].reshape(KM, dim, dim)[:K].copy())
+
+
+def em_hyper_vector(opt: dict, W0inv: np.ndarray) -> np.ndarray:
+    """[alpha0, epsilon0, beta0, v0, m0[8], diag(W0^-1)[8]] of (clipped) options."""
+    dim = len(opt["mu0"])
+    h = np.zeros(20)
+    h[:4] = opt["alpha0"], opt["epsilon0"], opt["beta0"], opt["v0"]
+    h[4:4 + dim] = opt["mu0"]
+    h[12:20] = 1.0
+    h[12:12 + dim] = np.diag(W0inv)
+    return h
+
+
+def fused_supported(opt: dict, Ks, dim: int) -> bool:
+    """The batched EM covers the EM loop without fix_clusters / fix_cov for K <= 8 and
+    dim <= 8; everything else stays with the loop engine."""
+    return (not opt.get("fix_clusters", 0) and opt.get("fix_cov") is None
+            and max(int(k) for k in np.atleast_1d(Ks)) <= FUSED_MAX_K and dim <= FUSED_MAX_DIM)
+
+
+def _check_engine(engine: str) -> bool:
+    if engine not in ("loop", "fused"):
+        raise ValueError("engine is 'loop' or 'fused'")
+    return engine == "fused"
+
+
+def _initial_posterior(subjects, s: int, K: int, opt: dict, init: dict) -> dict:
+    """vbhmm_init for one run: ``init`` is a GMM (prior, mean, cov) or an HMM whose own
+    posterior starts the run ('inithmm')."""
+    if "varpar" in init:
+        return vbhmm_init([subjects.X[s]], K, dict(opt, initmode="inithmm", inithmm=init), None)
+    o = dict(opt)
+    if o.get("initmode") == "inithmm":
+        o["initmode"] = "random"
+    return vbhmm_init([subjects.X[s]], K, o, init)
+
+
+def _em_runs_desc(subjects, sub: np.ndarray, Ks: np.ndarray, post: np.ndarray, KM: int):
+    import torch
+    from . import _capi
+    dev = subjects.device
+    t = dict(sub=torch.from_numpy(np.ascontiguousarray(sub, dtype=np.int32)).to(dev),
+             K=torch.from_numpy(np.ascontiguousarray(Ks, dtype=np.int32)).to(dev),
+             post=torch.from_numpy(np.ascontiguousarray(post, dtype=np.float64)).to(dev))
+    return _capi.EmRunsT(len(sub), KM, _capi.ptr(t["sub"]), _capi.ptr(t["K"]), _capi.ptr(t["post"])), t
+
+
+def vbhmm_em_gamma(subjects, items, chunk_runs: int = 0) -> list:
+    """gamma of the E-step at a posterior, for a list of (subject index, varpar): one
+    fused call (vbhmm_em_gamma, include/vbhmm_em.h).  Returns per item the list over the
+    subject's sequences of [K][T_n] arrays (the ``gamma`` field of vbhmm_em)."""
+    import ctypes
+    import torch
+    from . import _capi
+    if not items:
+        return []
+    lib = _capi.lib()
+    dim, dev = subjects.dim, subjects.device
+    Ks = np.array([len(np.reshape(vp["alpha"], -1)) for _, vp in items])
+    KM = 4 if Ks.max() <= 4 else 8
+    sub = np.array([s for s, _ in items])
+    post = np.stack([pack_posterior(vp, K, KM, dim) for (_, vp), K in zip(items, Ks)])
+    rn, keep = _em_runs_desc(subjects, sub, Ks, post, KM)
+    rows = np.zeros(len(items) + 1, dtype=np.int64)
+    rows[1:] = np.cumsum(subjects.obs[sub])
+    d_rows = torch.from_numpy(rows[:-1].copy()).to(dev)
+    gam = torch.zeros((max(int(rows[-1]), 1), KM), dtype=torch.float64, device=dev)
+    status = torch.zeros(len(items), dtype=torch.int32, device=dev)
+    sd = subjects.desc()
+    nb = int(lib.vbhmm_em_batch_workspace_bytes(ctypes.byref(sd), len(items), KM, chunk_runs))
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _capi.check(lib.vbhmm_em_gamma(ctypes.byref(sd), ctypes.byref(rn), _capi.ptr(gam), _capi.ptr(d_rows),
+                                   _capi.ptr(status), chunk_runs, _capi.ptr(ws), ws.numel(), stream),
+                "vbhmm_em_gamma")
+    g = gam.cpu().numpy()
+    if int(status.max().item()) != 0:
+        raise _capi.VbhemError("vbhmm_em_gamma: a run's subject is out of range")
+    del keep
+    out = []
+    for i, (s, K) in enumerate(zip(sub, Ks)):
+        gi = g[rows[i]:rows[i + 1], :K]
+        cut = np.concatenate([[0], np.cumsum(subjects.lens[s])])
+        out.append([gi[cut[n]:cut[n + 1]].T.copy() for n in range(len(subjects.lens[s]))])
+    return out
+
+
+def em_output_pdf(hmm: dict) -> dict:
+    """The output Gaussians of vbhmm_em.m:394-408 from the posterior (W, v), in place."""
+    vp = hmm["varpar"]
+    K, dim = vp["m"].shape
+    pdf = []
+    for k in range(K):
+        Ck = np.linalg.inv(vp["W"][k]) / ((vp["v"][k] - dim - 1) if vp["v"][k] > dim + 1 else vp["v"][k])
+        pdf.append(dict(mean=vp["m"][k].copy(), cov=0.5 * (Ck + Ck.T)))
+    hmm["pdf"] = pdf
+    return hmm
+
+
+def fill_gamma(subjects, hmms: Sequence[dict], chunk_runs: int = 0) -> None:
+    """The ``gamma`` field of results of :func:`vbhmm_em_batch` (the E-step of the kept
+    last-E-step posterior), in one fused call; a result that has it already is left."""
+    todo = [h for h in hmms if "gamma" not in h]
+    for h, g in zip(todo, vbhmm_em_gamma(subjects, [(h["subject"], h["varpar_estep"]) for h in todo],
+                                         chunk_runs)):
+        h["gamma"] = g
+
+
+def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = False, gamma: bool = False,
+                   finish: bool = True, chunk_runs: int = 0, timing: Optional[dict] = None) -> list:
+    """The EM of :func:`vbhmm_em` for every run of ``runs`` in one fused call on the GPU
+    (vbhmm_em_batch, include/vbhmm_em.h): no host round trip inside the loop.
+
+    ``subjects`` is a :class:`vbhmm.SubjectBatch`; ``runs`` a list of (subject index, K,
+    gmm) or (subject index, K, inithmm); the initial posteriors come from
+    :func:`vbhmm_init` on the host.  One dict per run with the fields of vbhmm_em's
+    result (``LLs`` with keep_LLs, ``gamma`` with gamma=True through one more fused call,
+    ``dLL`` with opt['calc_LLderiv'], ``pdf`` unless finish=False: see
+    :func:`em_output_pdf`), plus ``subject``, ``status`` and ``varpar_estep``, the
+    posterior at the last E-step (``gamma``, ``dLL``, ``N1``, ``N``, ``M`` belong to it).
+    K <= 8 and dim <= 8; no fix_clusters / fix_cov.  ``timing`` (a dict) receives the
+    seconds of the call's three parts: init (vbhmm_init + packing, host), device (the
+    fused call up to the copy back), unpack (host)."""
+    import ctypes
+    import time
+    import torch
+    t0 = time.perf_counter()
+    from . import _capi
+    dim = subjects.dim
+    if device is not None and torch.device(device).type != subjects.device.type:
+        raise ValueError("the runs execute where the subjects live")
+    if opt.get("fix_clusters", 0) or opt.get("fix_cov") is not None:
+        raise ValueError("the batched EM has no fix_clusters / fix_cov")
+    opt, clipped = vbhmm_clip_hyps(opt)
+    if not len(runs):
+        return []
+    lib = _capi.lib()
+    dev = subjects.device
+    sub = np.array([int(r[0]) for r in runs])
+    Ks = np.array([int(r[1]) for r in runs])
+    KM = 4 if Ks.max() <= 4 else 8 if Ks.max() <= FUSED_MAX_K else 16
+    mixes = [_initial_posterior(subjects, s, K, opt, r[2]) for s, K, r in zip(sub, Ks, runs)]
+    W0inv, W0mode = mixes[0]["W0inv"], mixes[0]["W0mode"]
+    PL, SL = em_post_len(KM, dim), em_stats_len(KM, dim)
+    post = np.stack([pack_posterior(mx, K, KM, dim) for mx, K in zip(mixes, Ks)])
+    rn, keep = _em_runs_desc(subjects, sub, Ks, post, KM)
+    hv = em_hyper_vector(opt, W0inv)
+    hy = _capi.EmHyperT(hv[0], hv[1], hv[2], hv[3], (ctypes.c_double * 8)(*hv[4:12]),
+                        (ctypes.c_double * 8)(*hv[12:20]))
+    max_iter = int(opt["maxIter"])
+    bo = _capi.EmBatchOptT(max_iter, float(opt["minDiff"]), int(chunk_runs))
+    R = len(runs)
+    f64 = torch.float64
+    o_post, o_est = (torch.zeros((R, PL), dtype=f64, device=dev) for _ in range(2))
+    o_stats = torch.zeros((R, SL), dtype=f64, device=dev)
+    o_LL = torch.zeros(R, dtype=f64, device=dev)
+    o_it, o_st = (torch.zeros(R, dtype=torch.int32, device=dev) for _ in range(2))
+    o_LLs = torch.zeros((R, max_iter), dtype=f64, device=dev) if keep_LLs else None
+    sd = subjects.desc()
+    nb = int(lib.vbhmm_em_batch_workspace_bytes(ctypes.byref(sd), R, KM, int(chunk_runs)))
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    t1 = time.perf_counter()
+    _capi.check(lib.vbhmm_em_batch(ctypes.byref(sd), ctypes.byref(rn), ctypes.byref(hy), ctypes.byref(bo),
+                                   _capi.ptr(o_post), _capi.ptr(o_est), _capi.ptr(o_stats), _capi.ptr(o_LL),
+                                   _capi.ptr(o_it), _capi.ptr(o_st), _capi.ptr(o_LLs), _capi.ptr(ws),
+                                   ws.numel(), stream), "vbhmm_em_batch")
+    h_post, h_est, h_stats = o_post.cpu().numpy(), o_est.cpu().numpy(), o_stats.cpu().numpy()
+    h_LL, h_it, h_st = o_LL.cpu().numpy(), o_it.cpu().numpy(), o_st.cpu().numpy()
+    h_LLs = o_LLs.cpu().numpy() if keep_LLs else None
+    t2 = time.perf_counter()
+    del keep
+    if (h_st == 3).any():
+        raise _capi.VbhemError("vbhmm_em_batch: a run's subject or K is out of range")
+    out = []
+    for r in range(R):
+        K = int(Ks[r])
+        vp, vpe, st = (unpack_posterior(h_post[r], K, KM, dim), unpack_posterior(h_est[r], K, KM, dim),
+                       unpack_stats(h_stats[r], K, KM, dim))
+        sc = vp["epsilon"].sum(1, keepdims=True)
+        unstable = int(h_st[r]) == 2
+        h = dict(prior=vp["alpha"] / vp["alpha"].sum(), trans=vp["epsilon"] / np.where(sc == 0, 1.0, sc),
+                 LL=float(h_LL[r]), iters=int(h_it[r]), unstable=unstable, status=EM_STATUS[int(h_st[r])],
+                 M=st["M"], N1=st["Nk1"], N=st["Nk"], varpar=vp, varpar_estep=vpe, clipped=clipped, dLL=None,
+                 subject=int(sub[r]))
+        if keep_LLs:
+            h["LLs"] = h_LLs[r, :h["iters"]].copy()
+        if opt.get("calc_LLderiv", 0):
+            # vbhmm_em.m:332-343: the derivatives at the last E-step, before its M-step
+            stt = dict(dim=dim, K=K, W0inv=W0inv, W0mode=W0mode)
+            if unstable:
+                with np.errstate(all="ignore"):
+                    d = vbhmm_em_lb_derivs(stt, opt, vpe, dict(logLambdaTilde=np.zeros(K), logPiTilde=np.zeros(K),
+                                                                logATilde=np.zeros((K, K))), clipped)
+                h["dLL"] = {k: np.full_like(np.asarray(g, dtype=float), np.nan) for k, g in d.items()}
+            else:
+                h["dLL"] = vbhmm_em_lb_derivs(stt, opt, vpe, vbhmm.prelude(vpe), clipped)
+        if finish:
+            em_output_pdf(h)
+        out.append(h)
+    if gamma:
+        fill_gamma(subjects, out, chunk_runs)
+    if timing is not None:
+        for k, v in (("init", t1 - t0), ("device", t2 - t1), ("unpack", time.perf_counter() - t2)):
+            timing[k] = timing.get(k, 0.0) + v
+    return out
+
+
+# ----------------------------------------------------------------------------
 # hyperparameter learning (vbhmm_em_hyp.m, get_hypinfo.m, uniqueLL.m)
 # ----------------------------------------------------------------------------
 VBHMM_HYPS = ("alpha0", "epsilon0", "v0", "beta0", "W0", "mu0")
@@ -413,16 +682,30 @@ def _set_hyps(X: np.ndarray, opt: dict, info: list) -> dict:
 
 
 def vbhmm_em_hyp(data: Sequence[np.ndarray], K: int, opt: dict, inithmm: dict, device="cuda",
-                 batch: Optional["vbhmm.SequenceBatch"] = None) -> dict:
+                 batch: Optional["vbhmm.SequenceBatch"] = None, engine: str = "loop",
+                 subjects: Optional["vbhmm.SubjectBatch"] = None, subject: int = 0) -> dict:
     """vbhmm_em_hyp.m:15-126: maximise the bound over the transformed
     hyperparameters (minimize_new.m, p.length = opt['hyp_length'], BFGS by default),
     every evaluation an EM run from ``inithmm`` with its derivatives (vbhmm_grad,
     :172-190), then one EM run at the optimum; the result carries ``learn_hyps``
-    (hypinfo names, opt_transhyp, opt_L, the optimised hyperparameters)."""
+    (hypinfo names, opt_transhyp, opt_L, the optimised hyperparameters).  With
+    engine="fused" every evaluation is one :func:`vbhmm_em_batch` call of one run
+    (``subjects`` / ``subject``: where ``data`` already lives on the GPU)."""
     from . import hyp
     dim = len(opt["mu0"])
     data = [np.asarray(a, dtype=np.float64).reshape(-1, dim) for a in data]
-    sb = batch if batch is not None else vbhmm.SequenceBatch(data, dim, device)
+    fused = _check_engine(engine) and fused_supported(opt, K, dim)
+    if fused:
+        if subjects is None:
+            subjects, subject = vbhmm.SubjectBatch([data], dim, device), 0
+
+        def run_em(o, last=False):
+            return vbhmm_em_batch(subjects, [(subject, K, o["inithmm"])], o, keep_LLs=True, gamma=last)[0]
+    else:
+        sb = batch if batch is not None else vbhmm.SequenceBatch(data, dim, device)
+
+        def run_em(o, last=False):
+            return vbhmm_em(data, K, o, batch=sb)
     info = vbhmm_hypinfo(opt.get("learn_hyps", 1) or 1, opt)
     base = dict(opt, initmode="inithmm", inithmm=inithmm)
     n_eval = [0]
@@ -430,7 +713,7 @@ def vbhmm_em_hyp(data: Sequence[np.ndarray], K: int, opt: dict, inithmm: dict, d
     def grad(X):
         o = _set_hyps(X, base, info)
         o["calc_LLderiv"] = 1
-        h = vbhmm_em(data, K, o, batch=sb)
+        h = run_em(o)
         n_eval[0] += 1
         return -h["LL"], np.concatenate([-np.atleast_1d(h["dLL"][i.derivname]).reshape(-1) for i in info])
 
@@ -442,7 +725,7 @@ def vbhmm_em_hyp(data: Sequence[np.ndarray], K: int, opt: dict, inithmm: dict, d
     Xopt, fX, nls = hyp.minimize(X0, grad, length=int(opt.get("hyp_length", 100)), method=methods[name])
     o2 = _set_hyps(Xopt, base, info)
     o2["calc_LLderiv"] = 0
-    h = vbhmm_em(data, K, o2, batch=sb)
+    h = run_em(o2, last=True)
     h["learn_hyps"] = dict(hypinfo=[i.optname for i in info], opt_transhyp=Xopt, opt_L=-fX[-1],
                            fX=fX, line_searches=nls, evaluations=n_eval[0],
                            vbopt={i.optname: o2[i.optname] for i in info})
@@ -450,51 +733,101 @@ def vbhmm_em_hyp(data: Sequence[np.ndarray], K: int, opt: dict, inithmm: dict, d
 
 
 def vbhmm_learn(data: Sequence[np.ndarray], Ks, opt: dict, device="cuda",
-                gmms: Optional[dict] = None) -> dict:
+                gmms: Optional[dict] = None, engine: str = "loop") -> dict:
     """vbhmm_learn.m (initmode 'random'): for each K, numtrials EM runs from random
     GMMs (seeded by opt['seed'], vbhmm_learn.m:443-451; K = 1 needs one); with
     opt['learn_hyps'] every unique trial (uniqueLL, 2 minDiff 10 apart) is re-run
     through :func:`vbhmm_em_hyp` (:482-552); keep the best bound; over several K,
     select by LL + gammaln(K+1) (:367-405).  ``gmms[K]`` = list of GMMs to inject
-    instead of random draws."""
+    instead of random draws.  engine="fused": the EM runs of every K and trial in one
+    :func:`vbhmm_em_batch` call (the loop engine where that does not apply)."""
     Ks = [int(k) for k in np.atleast_1d(Ks)]
     dim = len(opt["mu0"])
     data = [np.asarray(a, dtype=np.float64).reshape(-1, dim) for a in data]
+    if _check_engine(engine) and fused_supported(opt, Ks, dim):
+        return _learn_fused([data], Ks, opt, device, [gmms])[0]
     sb = vbhmm.SequenceBatch(data, dim, device)
     out_all = []
     for K in Ks:
-        rng = np.random.default_rng(opt["seed"])
-        if gmms is not None and K in gmms:
-            inits = list(gmms[K])
-        else:
-            numits = 1 if K == 1 else int(opt["numtrials"])
-            inits = [random_gmm(data, K, rng) for _ in range(numits)]
+        inits = _draw_inits(data, K, opt, gmms)
         trials = [vbhmm_em(data, K, opt, gmm=g, batch=sb) for g in inits]
-        LLall = np.array([h["LL"] for h in trials])
-        LLall_random, trials_random = LLall.copy(), list(trials)
-        learn = _do_learn_hyps(opt.get("learn_hyps", 0))
-        if learn or opt.get("keep_suboptimal_hmms", 0):
-            from .cluster import unique_ll   # uniqueLL.m
-            uniq = unique_ll(LLall, 2 * opt["minDiff"] * 10)
-        if learn:
-            LLall = np.full(len(trials), np.nan)
-            for it in uniq:
-                trials[it] = vbhmm_em_hyp(data, K, opt, trials_random[it], batch=sb)
-                LLall[it] = trials[it]["LL"]
-        best = trials[int(np.nanargmax(LLall))]
-        best["trials_LL"] = LLall
-        if opt.get("keep_suboptimal_hmms", 0):  # vbhmm_learn.m:600-602 (the random trials)
-            best["suboptimal_hmms"] = [trials_random[it] for it in uniq]
-        if learn:
-            best["trials_LL_random"] = LLall_random
-            if opt.get("keep_best_random_trial", 0):  # vbhmm_learn.m:587-596
-                tmp = trials_random[int(np.argmax(LLall_random))]
-                if opt.get("sortclusters"):
-                    tmp = vbhmm_standardize(tmp, opt["sortclusters"])
-                best["learn_hyps"]["hmm_best_random_trial"] = tmp
-        if opt.get("sortclusters"):  # vbhmm_learn.m:635-640
-            best = vbhmm_standardize(best, opt["sortclusters"])
-        out_all.append(best)
+        out_all.append(_learn_pick(data, K, opt, trials, lambda q: vbhmm_em_hyp(data, K, opt, q, batch=sb)))
+    return _learn_select(out_all, Ks, opt)
+
+
+def _learn_fused(datas, Ks: list, opt: dict, device, gmms_list, subjects=None) -> list:
+    """vbhmm_learn for every subject under the fused engine: the GMMs of all subjects, Ks
+    and trials are drawn on the host exactly as the loop engine draws them, ONE
+    :func:`vbhmm_em_batch` call runs them all (ordered by subject, so neighbouring
+    wavefronts read the same data), then each subject's trials go through the same
+    selection.  Output Gaussians are computed for every run (they are cheap next to the
+    GMM fits); gamma comes from one more fused call for each (subject, K)'s best random
+    trial."""
+    dim = len(opt["mu0"])
+    sbt = subjects if subjects is not None else vbhmm.SubjectBatch(datas, dim, device)
+    runs, where = [], []
+    for s, data in enumerate(sbt.datas):
+        g = gmms_list[s] if gmms_list is not None else None
+        for K in Ks:
+            for init in _draw_inits(data, K, opt, g):
+                runs.append((s, K, init))
+                where.append((s, K))
+    res = vbhmm_em_batch(sbt, runs, opt, keep_LLs=True)
+    per = {}
+    for w, h in zip(where, res):
+        per.setdefault(w, []).append(h)
+    fill_gamma(sbt, [t[int(np.argmax([h["LL"] for h in t]))] for t in per.values()])
+    out = []
+    for s, data in enumerate(sbt.datas):
+        out_all = [_learn_pick(data, K, opt, per[(s, K)],
+                               lambda q, K=K: vbhmm_em_hyp(data, K, opt, q, engine="fused", subjects=sbt, subject=s))
+                   for K in Ks]
+        out.append(_learn_select(out_all, Ks, opt))
+    return out
+
+
+def _draw_inits(data, K: int, opt: dict, gmms: Optional[dict]) -> list:
+    """vbhmm_learn.m:443-451: the GMMs of one K's random trials, each K from its own
+    generator seeded by opt['seed'] (K = 1 needs one trial), or the injected ones."""
+    rng = np.random.default_rng(opt["seed"])
+    if gmms is not None and K in gmms:
+        return list(gmms[K])
+    numits = 1 if K == 1 else int(opt["numtrials"])
+    return [random_gmm(data, K, rng) for _ in range(numits)]
+
+
+def _learn_pick(data, K: int, opt: dict, trials: list, em_hyp) -> dict:
+    """vbhmm_learn.m:453-640 for one K: the best of the trials' bounds, after
+    hyperparameter learning on the unique ones (``em_hyp(trial)``) where asked for."""
+    LLall = np.array([h["LL"] for h in trials])
+    LLall_random, trials_random = LLall.copy(), list(trials)
+    learn = _do_learn_hyps(opt.get("learn_hyps", 0))
+    if learn or opt.get("keep_suboptimal_hmms", 0):
+        from .cluster import unique_ll   # uniqueLL.m
+        uniq = unique_ll(LLall, 2 * opt["minDiff"] * 10)
+    if learn:
+        LLall = np.full(len(trials), np.nan)
+        for it in uniq:
+            trials[it] = em_hyp(trials_random[it])
+            LLall[it] = trials[it]["LL"]
+    best = trials[int(np.nanargmax(LLall))]
+    best["trials_LL"] = LLall
+    if opt.get("keep_suboptimal_hmms", 0):  # vbhmm_learn.m:600-602 (the random trials)
+        best["suboptimal_hmms"] = [trials_random[it] for it in uniq]
+    if learn:
+        best["trials_LL_random"] = LLall_random
+        if opt.get("keep_best_random_trial", 0):  # vbhmm_learn.m:587-596
+            tmp = trials_random[int(np.argmax(LLall_random))]
+            if opt.get("sortclusters"):
+                tmp = vbhmm_standardize(tmp, opt["sortclusters"])
+            best["learn_hyps"]["hmm_best_random_trial"] = tmp
+    if opt.get("sortclusters"):  # vbhmm_learn.m:635-640
+        best = vbhmm_standardize(best, opt["sortclusters"])
+    return best
+
+
+def _learn_select(out_all: list, Ks: list, opt: dict) -> dict:
+    """vbhmm_learn.m:367-424: over several K, select by LL + gammaln(K+1)."""
     if len(Ks) == 1:
         return out_all[0]
     LLk = np.array([h["LL"] for h in out_all]) + gammaln(np.array(Ks) + 1.0)
@@ -523,12 +856,13 @@ def vbhmm_permute(hmm: dict, cl) -> dict:
     out["pdf"] = [hmm["pdf"][k] for k in cl]
     if "gamma" in hmm:
         out["gamma"] = [np.asarray(g)[cl] for g in hmm["gamma"]]
-    if "varpar" in hmm:
-        vp = hmm["varpar"]
-        out["varpar"] = dict(vp, epsilon=np.asarray(vp["epsilon"])[np.ix_(cl, cl)],
-                             alpha=np.asarray(vp["alpha"])[cl], beta=np.asarray(vp["beta"])[cl],
-                             v=np.asarray(vp["v"])[cl], m=np.asarray(vp["m"])[cl],
-                             W=np.asarray(vp["W"])[cl])
+    for key in ("varpar", "varpar_estep"):
+        if key not in hmm:
+            continue
+        vp = hmm[key]
+        out[key] = dict(vp, epsilon=np.asarray(vp["epsilon"])[np.ix_(cl, cl)],
+                        alpha=np.asarray(vp["alpha"])[cl], beta=np.asarray(vp["beta"])[cl],
+                        v=np.asarray(vp["v"])[cl], m=np.asarray(vp["m"])[cl], W=np.asarray(vp["W"])[cl])
     return out
 
 
@@ -577,19 +911,54 @@ def _do_learn_hyps(v) -> bool:
 
 
 def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, device="cuda",
-                      gmms: Optional[list] = None):
+                      gmms: Optional[list] = None, engine: str = "loop"):
     """vbhmm_learn_batch.m: one vbhmm_learn per subject; returns (hmms, LLs).  With
     opt['learn_hyps_batch'] (:84-189) one set of hyperparameters shared by every
     subject: each subject's unique random trials (keep_suboptimal_hmms) seed EM runs,
     and BFGS (minimize_new.m, length 100) minimises the mean over subjects of the
     best -(LL + gammaln(K+1)) among that subject's runs (vbhmm_grad_batch_parfor,
-    :347-457); the returned HMMs are the final run's, each with its ``vbopt``."""
+    :347-457); the returned HMMs are the final run's, each with its ``vbopt``.
+
+    engine="fused": the EM runs of all subjects, Ks and trials are one
+    :func:`vbhmm_em_batch` call, and every evaluation of the shared-hyperparameter
+    objective is one call over all (subject, suboptimal HMM) runs; fix_clusters,
+    fix_cov, K > 8 and dim > 8 stay with the loop engine."""
     lhb = opt.get("learn_hyps_batch", 0)
+    Ks = [int(k) for k in np.atleast_1d(Ks)]
+    fused = _check_engine(engine) and fused_supported(opt, Ks, len(opt["mu0"]))
     if not (isinstance(lhb, (list, tuple)) or lhb):
+        if fused:
+            hmms = _learn_fused(datas, Ks, opt, device, gmms)
+            return hmms, np.array([h["LL"] for h in hmms])
         hmms = [vbhmm_learn(d, Ks, opt, device, gmms[i] if gmms is not None else None)
                 for i, d in enumerate(datas)]
         return hmms, np.array([h["LL"] for h in hmms])
     from . import hyp
+    grad_batch, X0, info, opt = hyps_batch_objective(datas, Ks, opt, device, gmms, engine)
+    methods = {"minimize-bfgs": "BFGS", "minimize-lbfgs": "LBFGS", "minimize-cg": "CG"}
+    name = opt.get("minimizer", "minimize-bfgs")
+    if name not in methods:
+        raise ValueError("bad minimizer specified")
+    Xopt, fX, nls = hyp.minimize(X0, grad_batch, length=100, method=methods[name])
+    _, _, hmms = grad_batch(Xopt, keep=True)
+    for h in hmms:
+        h["learn_hyps_batch"] = dict(hypinfo=[i.optname for i in info], opt_transhyp=Xopt,
+                                     opt_L=-fX[-1], fX=fX, line_searches=nls)
+    if opt.get("sortclusters"):  # vbhmm_learn_batch.m:202-209
+        hmms = [vbhmm_standardize(h, opt["sortclusters"]) for h in hmms]
+    return hmms, np.array([h["LL"] for h in hmms])
+
+
+def hyps_batch_objective(datas, Ks, opt: dict, device="cuda", gmms: Optional[list] = None,
+                         engine: str = "loop"):
+    """The objective of opt['learn_hyps_batch'] (vbhmm_grad_batch_parfor,
+    vbhmm_learn_batch.m:347-457): learns every subject's unique random trials, then
+    returns (grad_batch, X0, hypinfo, options) with grad_batch(X, keep=False) -> (mean
+    over subjects of the best -(LL + gammaln(K+1)), its gradient[, the best HMMs])."""
+    from . import hyp
+    lhb = opt["learn_hyps_batch"]
+    Ks = [int(k) for k in np.atleast_1d(Ks)]
+    fused = _check_engine(engine) and fused_supported(opt, Ks, len(opt["mu0"]))
     if not isinstance(lhb, (list, tuple)):
         if lhb != 1:
             raise ValueError("learn_hyps_batch not set properly")
@@ -598,12 +967,42 @@ def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, devi
     info = vbhmm_hypinfo(list(lhb), opt)
     dim = len(opt["mu0"])
     datas = [[np.asarray(a, dtype=np.float64).reshape(-1, dim) for a in d] for d in datas]
-    batches = [vbhmm.SequenceBatch(d, dim, device) for d in datas]
     iopt = dict(opt, keep_suboptimal_hmms=1)
-    inithmms = [vbhmm_learn(d, Ks, iopt, device, gmms[i] if gmms is not None else None)
-                for i, d in enumerate(datas)]
+    if fused:
+        sbt = vbhmm.SubjectBatch(datas, dim, device)
+        inithmms = _learn_fused(datas, Ks, iopt, device, gmms, subjects=sbt)
+    else:
+        batches = [vbhmm.SequenceBatch(d, dim, device) for d in datas]
+        inithmms = [vbhmm_learn(d, Ks, iopt, device, gmms[i] if gmms is not None else None)
+                    for i, d in enumerate(datas)]
+
+    def grad_batch_fused(X, keep=False):
+        # one call over every (subject, suboptimal HMM) run; then the loop engine's choice
+        o = _set_hyps(X, dict(opt, initmode="inithmm", calc_LLderiv=1), info)
+        runs = [(n, len(q["pdf"]), q) for n in range(len(datas)) for q in inithmms[n]["suboptimal_hmms"]]
+        res = vbhmm_em_batch(sbt, runs, o, keep_LLs=True)
+        nL, dnL, out, i = 0.0, 0.0, [], 0
+        for n in range(len(datas)):
+            best = None
+            for q in inithmms[n]["suboptimal_hmms"]:
+                qh, K = res[i], len(q["pdf"])
+                i += 1
+                qnL = -qh["LL"] - gammaln(K + 1)
+                if best is None or qnL < best[0]:   # MATLAB min: the first of equal values
+                    best = (qnL, qh)
+            nL += best[0]
+            dnL = dnL - np.concatenate([np.atleast_1d(best[1]["dLL"][i_.derivname]).reshape(-1) for i_ in info])
+            if keep:
+                best[1]["vbopt"] = {i_.optname: o[i_.optname] for i_ in info}
+                out.append(best[1])
+        if keep:
+            fill_gamma(sbt, out)
+        N = len(datas)
+        return (nL / N, dnL / N, out) if keep else (nL / N, dnL / N)
 
     def grad_batch(X, keep=False):
+        if fused:
+            return grad_batch_fused(X, keep)
         nL, dnL, out = 0.0, 0.0, []
         for n, d in enumerate(datas):
             o = _set_hyps(X, dict(opt, initmode="inithmm", calc_LLderiv=1), info)
@@ -622,19 +1021,7 @@ def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, devi
         N = len(datas)
         return (nL / N, dnL / N, out) if keep else (nL / N, dnL / N)
 
-    methods = {"minimize-bfgs": "BFGS", "minimize-lbfgs": "LBFGS", "minimize-cg": "CG"}
-    name = opt.get("minimizer", "minimize-bfgs")
-    if name not in methods:
-        raise ValueError("bad minimizer specified")
-    X0 = hyp.init_x(opt, info)
-    Xopt, fX, nls = hyp.minimize(X0, grad_batch, length=100, method=methods[name])
-    _, _, hmms = grad_batch(Xopt, keep=True)
-    for h in hmms:
-        h["learn_hyps_batch"] = dict(hypinfo=[i.optname for i in info], opt_transhyp=Xopt,
-                                     opt_L=-fX[-1], fX=fX, line_searches=nls)
-    if opt.get("sortclusters"):  # vbhmm_learn_batch.m:202-209
-        hmms = [vbhmm_standardize(h, opt["sortclusters"]) for h in hmms]
-    return hmms, np.array([h["LL"] for h in hmms])
+    return grad_batch, hyp.init_x(opt, info), info, opt
 
 
 def vbhmm_remove_empty(hmm: dict, thresh: float = 1.0) -> dict:

@@ -1,0 +1,81 @@
+// tests/vbhmmemcheck/walker_main.cpp -- TEST-ONLY stand-alone program: the serial walker of
+// csrc/vbhmm_em_run.h on seeded inputs, for a run under the address and undefined-behaviour
+// sanitizers on the CPU (`make vbhmmem_sanitize`; plain C++, no device compiler).  It
+// walks every shape class the kernel has: KM = 4 and 8, dim = 2 and 8, 70 sequences with
+// lengths 1..49 (T = 1 included), a single sequence, and an unstable run.
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "vbhmm_em_run.h"
+
+using namespace vbhem::emrun;
+
+namespace {
+
+struct Lcg {
+  unsigned long long s;
+  double uni() {
+    s = s * 6364136223846793005ULL + 1442695040888963407ULL;
+    return (double)(s >> 11) / 9007199254740992.0;
+  }
+  double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
+};
+
+template <int KM>
+int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool break_W) {
+  Lcg g{seed};
+  std::vector<int> off(N + 1, 0);
+  for (int n = 0; n < N; ++n) off[n + 1] = off[n] + (n == 0 ? 1 : 1 + (int)(g.uni() * maxlen));
+  const int obs = off[N];
+  std::vector<double> x((size_t)obs * dim);
+  for (int p = 0; p < obs; ++p) {
+    const int z = g.uni() < 0.5;
+    for (int a = 0; a < dim; ++a) x[(size_t)p * dim + a] = (z ? 150.0 : 210.0) + 10.0 * a + 20.0 * g.normal();
+  }
+  Hyper h;
+  h.alpha0 = h.epsilon0 = h.beta0 = 1.0;
+  h.v0 = dim + 8.0;
+  for (int a = 0; a < kMaxDim; ++a) {
+    h.m0[a] = 180.0;
+    h.W0inv[a] = 1000.0;
+  }
+  const int PL = post_len(KM, dim), SL = stats_len(KM, dim);
+  std::vector<double> post(PL, 1.0), est(PL), st(SL), LLs(30, 0.0);
+  double *alpha = post.data(), *eps = alpha + KM, *beta = eps + KM * KM, *v = beta + KM, *m = v + KM,
+         *W = m + KM * dim;
+  for (int k = 0; k < K; ++k) {
+    alpha[k] = 1.0 + (double)N / K;
+    beta[k] = 1.0 + (double)obs / K;
+    v[k] = h.v0 + (double)obs / K + 1;
+    for (int j = 0; j < K; ++j) eps[k * KM + j] = 1.0 + (double)N / K;
+    for (int a = 0; a < dim; ++a) {
+      m[k * dim + a] = 150.0 + 60.0 * k / (K > 1 ? K - 1 : 1) + 10.0 * a;
+      for (int b = 0; b < dim; ++b) W[(k * dim + a) * dim + b] = a == b ? 1.0 / (400.0 * v[k]) : 0.0;
+    }
+  }
+  if (break_W) W[0] = -W[0];
+  std::vector<double> gm((size_t)obs * KM), lr((size_t)obs * KM), cs(obs), mx(obs), sq((size_t)N * seq_len(KM));
+  const Work<KM> w{gm.data(), lr.data(), cs.data(), mx.data(), sq.data()};
+  const Subject s{N, off.data(), x.data()};
+  const RunResult r = run_serial<KM>(K, dim, s, h, 30, 1e-5, post.data(), est.data(), st.data(), LLs.data(), w);
+  std::printf("KM=%d K=%d dim=%d N=%d obs=%d: LL=%.12g iters=%d status=%d\n", KM, K, dim, N, obs, r.LL, r.iters,
+              r.status);
+  if (break_W) return !(r.status == kUnstable && r.iters == 1 && std::isinf(r.LL));
+  return !(std::isfinite(r.LL) && r.status != kUnstable && r.iters >= 1);
+}
+
+}  // namespace
+
+int main() {
+  int bad = 0;
+  bad += one_case<4>(1, 2, 70, 49, 1, false);
+  bad += one_case<4>(3, 2, 70, 49, 2, false);
+  bad += one_case<4>(4, 3, 65, 5, 3, false);
+  bad += one_case<8>(5, 2, 64, 5, 4, false);
+  bad += one_case<8>(8, 8, 40, 12, 5, false);
+  bad += one_case<4>(2, 2, 1, 9, 6, false);
+  bad += one_case<4>(2, 2, 30, 5, 7, true);
+  std::printf(bad ? "FAILED %d\n" : "walker OK\n", bad);
+  return bad != 0;
+}
