@@ -254,6 +254,18 @@ def ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
+def stream(device) -> ctypes.c_void_p:
+    """torch's current stream on ``device``, as the C ABI's ``void *stream``."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def workspace(nbytes: int, device, align: int = 1) -> torch.Tensor:
+    """An uninitialised uint8 buffer on ``device`` for a ``*_workspace_bytes`` answer:
+    ``nbytes`` long, and at least ``align`` bytes (the C ABI refuses a null workspace;
+    the entries that ask for 16-byte alignment also take 16 bytes as their least size)."""
+    return torch.empty((max(int(nbytes), align),), dtype=torch.uint8, device=device)
+
+
 def timing_enable(on: bool = True, fb_only: bool = False) -> None:
     """Kernel timing on this thread: every timed launch, or (fb_only) the fb
     launches alone (two events per E-step)."""

@@ -118,7 +118,7 @@ class DeviceEngine:
         self._rowmin, self._rowmax = rowmin, rowmax
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._capi.stream(self.device)
 
     def _int(self, a) -> torch.Tensor:
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)

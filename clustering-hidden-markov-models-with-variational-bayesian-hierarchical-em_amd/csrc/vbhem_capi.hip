@@ -163,16 +163,15 @@ int fail(int code, const std::string &msg) {
   return code;
 }
 
-int hip_fail(hipError_t e, const char *where) {
-  return fail(VBHEM_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e));
-}
-
 }  // namespace
 
 // shared with the other C-ABI translation units (vbhmm_fb.hip): vbhem_last_error()
 int vbhem::set_error(int code, const std::string &msg) { return fail(code, msg); }
 
 namespace {
+
+using vbhem::align_up;
+using vbhem::hip_fail;
 
 constexpr size_t kLdsLimit = 160 * 1024;          // gfx950 LDS per workgroup
 constexpr int kFbMaxThreads = 512;                // fb_pairs_kernel launch bound
@@ -182,7 +181,6 @@ constexpr size_t kGroupBudget = (size_t)8 << 30;  // per-pair buffers per group 
 constexpr int kMaxSlabs = 512;    // statistics chunks (= resp/stats blocks per group)
 
 inline int odd_up(int x) { return (x % 2 == 0) ? x + 1 : x; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct FbPlan {
   vbhem::FbArgs a;

@@ -9,12 +9,19 @@
 #include <string>
 #include <tuple>
 
+#include "vbhem_estep.h"     // status codes
 #include "vbhem_switches.h"  // struct Switches, switches()
 
 namespace vbhem {
 
 // record `msg` for vbhem_last_error() and return `code` (vbhem_capi.hip)
 int set_error(int code, const std::string &msg);
+// VBHEM_ERR_HIP with the message "<where>: <HIP's text for e>"
+static inline int hip_fail(hipError_t e, const char *where) {
+  return set_error(VBHEM_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e));
+}
+
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Host-side launch helpers: the dynamic-LDS attribute, the occupancy query and
 // the CU count are per (device, kernel, block, LDS) facts, so they are asked

@@ -135,7 +135,7 @@ int vbhem_rccl_allreduce_to(void *comm, double *buf, size_t n, double *out_dev, 
                      out_dev, buf, n);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? VBHEM_OK
-                         : vbhem::set_error(VBHEM_ERR_HIP, std::string("stats_copy_kernel: ") + hipGetErrorString(e));
+                         : vbhem::hip_fail(e, "stats_copy_kernel");
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@
 #include "vbhem_internal.h"
 #include "vbhmm_ccfd.h"
 #include "vbhmm_ccfd_row.h"
+#include "vbhmm_hmmset.h"
 #include "vbhmm_score_pair.h"
 
 namespace vbhem {
@@ -45,7 +46,6 @@ using namespace ccfd;
 constexpr int kDistThreads = 128;  // lanes = sequences per tile
 constexpr int kRowThreads = 256;
 constexpr int kRowWaves = kRowThreads / 64;
-constexpr int kPrepHead = 8;  // doubles before the blocks of a prepared buffer (vbhmm_score.hip)
 
 struct DistArgs {
   int H, d, diag, tiles;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kDistThreads) void ccfd_own_kernel(const DistArgs p
   __shared__ double sh[BlockLen<KB, DB>::value];
   const int2 t = p.own_tiles[blockIdx.x];
   const double *blk = p.blocks + (size_t)t.x * p.L.stride;
-  for (int q = threadIdx.x; q < p.L.stride; q += kDistThreads) sh[q] = blk[q];
+  hmmset::stage_block(sh, blk, p.L.stride, kDistThreads);
   __syncthreads();
   const int n = t.y + threadIdx.x;
   if (n >= p.seg[t.x + 1]) return;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kDistThreads) void ccfd_cross_kernel(const DistArgs
   const int4 t = p.cross_tiles[blockIdx.x % p.tiles];
   const int n0 = t.x, cnt = t.y, s0 = t.z, nseg = t.w;
   const double *blk = p.blocks + (size_t)j * p.L.stride;
-  for (int q = tid; q < p.L.stride; q += kDistThreads) sh[q] = blk[q];
+  hmmset::stage_block(sh, blk, p.L.stride, kDistThreads);
   __syncthreads();
   const Hmm m = view(p.L, sh, p.diag != 0);
   if (cnt > kDistThreads) {  // one long segment, in passes; uniform over the workgroup
@@ -287,8 +287,6 @@ __global__ __launch_bounds__(kRowThreads) void ccfd_border_kernel(const double *
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-size_t align16(size_t b) { return (b + 15) / 16 * 16; }
-
 struct WsLayout {
   size_t own, own_tiles, cross_tiles, total;
   long long max_own_tiles;
@@ -298,14 +296,10 @@ WsLayout ws_layout(int H, long long n_total) {
   WsLayout w;
   w.max_own_tiles = (long long)H + n_total / kDistThreads + 1;
   w.own = 0;
-  w.own_tiles = align16((size_t)(n_total > 0 ? n_total : 1) * sizeof(double));
-  w.cross_tiles = w.own_tiles + align16((size_t)w.max_own_tiles * sizeof(int2));
-  w.total = w.cross_tiles + align16((size_t)(H > 0 ? H : 1) * sizeof(int4));
+  w.own_tiles = align_up((size_t)(n_total > 0 ? n_total : 1) * sizeof(double), 16);
+  w.cross_tiles = w.own_tiles + align_up((size_t)w.max_own_tiles * sizeof(int2), 16);
+  w.total = w.cross_tiles + align_up((size_t)(H > 0 ? H : 1) * sizeof(int4), 16);
   return w;
-}
-
-int hip_fail(const char *what, hipError_t e) {
-  return set_error(VBHEM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 int check_matrix(const double *D, int N, const char *who) {
@@ -329,17 +323,13 @@ int vbhmm_ccfd_distance(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
                         double *D_dev, double *rowmin_dev, double *rowmax_dev, void *stream) {
   using namespace vbhem;
   if (!m || !s) return set_error(VBHEM_ERR_ARG, "vbhmm_ccfd_distance: null HMM set or sequences");
-  if (m->H < 0 || m->KM < 1 || m->dim < 1 || (m->covmode != VBHEM_COV_DIAG && m->covmode != VBHEM_COV_FULL))
-    return set_error(VBHEM_ERR_ARG, "invalid HMM set (need H>=0, KM>=1, dim>=1, covmode diag or full)");
-  if (m->KM > kMaxStates || m->dim > kMaxDim)
-    return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_ccfd: at most 16 states and 8 dimensions supported");
-  if (s->N < 0 || s->dim != m->dim)
-    return set_error(VBHEM_ERR_ARG, "invalid sequences (need N>=0, the HMMs' dim)");
+  int rc = hmmset::check_set(m, "vbhmm_ccfd");
+  if (rc == VBHEM_OK) rc = hmmset::check_seqs(m, s);
+  if (rc != VBHEM_OK) return rc;
   const int H = m->H, N = s->N;
   if (H == 0) return VBHEM_OK;
   if (!prepared_dev || !seg_offsets_dev || !D_dev || !rowmin_dev || !rowmax_dev)
     return set_error(VBHEM_ERR_ARG, "vbhmm_ccfd_distance: null prepared buffer, segment offsets or output");
-  if (N > 0 && (!s->offsets || !s->x)) return set_error(VBHEM_ERR_ARG, "null sequence array");
   const WsLayout w = ws_layout(H, N);
   if (!workspace_dev || workspace_bytes < w.total)
     return set_error(VBHEM_ERR_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
@@ -351,7 +341,7 @@ int vbhmm_ccfd_distance(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
   std::vector<int> seg((size_t)H + 1);
   hipError_t e = hipMemcpyAsync(seg.data(), seg_offsets_dev, seg.size() * sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail("vbhmm_ccfd_distance (segment offsets)", e);
+  if (e != hipSuccess) return hip_fail(e, "vbhmm_ccfd_distance (segment offsets)");
   if (seg[0] != 0 || seg[H] != N) return set_error(VBHEM_ERR_ARG, "segment offsets must run from 0 to the sequence count");
   for (int i = 0; i < H; ++i)
     if (seg[i + 1] < seg[i]) return set_error(VBHEM_ERR_ARG, "segment offsets must not decrease");
@@ -380,7 +370,7 @@ int vbhmm_ccfd_distance(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
   DistArgs a{};
   a.H = H; a.d = m->dim; a.diag = m->covmode == VBHEM_COV_DIAG; a.tiles = (int)cross_tiles.size();
   a.L = make_layout(m->KM, m->dim);
-  a.blocks = static_cast<const double *>(prepared_dev) + kPrepHead;
+  a.blocks = hmmset::blocks(prepared_dev);
   a.offsets = s->offsets; a.seg = seg_offsets_dev; a.x = s->x;
   a.own = reinterpret_cast<double *>(ws + w.own);
   a.own_tiles = reinterpret_cast<const int2 *>(ws + w.own_tiles);
@@ -392,18 +382,18 @@ int vbhmm_ccfd_distance(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
     e = hipMemcpyAsync(ws + w.cross_tiles, cross_tiles.data(), cross_tiles.size() * sizeof(int4),
                        hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the tables are pageable host memory
-  if (e != hipSuccess) return hip_fail("vbhmm_ccfd_distance (tile tables)", e);
+  if (e != hipSuccess) return hip_fail(e, "vbhmm_ccfd_distance (tile tables)");
 
   if (!own_tiles.empty()) {
     e = dispatch(m->KM, m->dim, LaunchOwn{a, (unsigned)own_tiles.size(), st});
-    if (e != hipSuccess) return hip_fail("ccfd_own_kernel", e);
+    if (e != hipSuccess) return hip_fail(e, "ccfd_own_kernel");
   }
   e = dispatch(m->KM, m->dim, LaunchCross{a, (unsigned)((long long)a.tiles * H), st});
-  if (e != hipSuccess) return hip_fail("ccfd_cross_kernel", e);
+  if (e != hipSuccess) return hip_fail(e, "ccfd_cross_kernel");
   hipLaunchKernelGGL((ccfd_sym_kernel<true>), dim3((unsigned)H), dim3(kRowThreads), 0, st, D_dev, H, rowmin_dev,
                      rowmax_dev);
   e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("ccfd_sym_kernel", e);
+  if (e != hipSuccess) return hip_fail(e, "ccfd_sym_kernel");
   return VBHEM_OK;
 }
 
@@ -415,7 +405,7 @@ int vbhmm_ccfd_rowstats(const double *D_dev, int N, double *rowmin_dev, double *
   hipLaunchKernelGGL((ccfd_sym_kernel<false>), dim3((unsigned)N), dim3(kRowThreads), 0,
                      static_cast<hipStream_t>(stream), const_cast<double *>(D_dev), N, rowmin_dev, rowmax_dev);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VBHEM_OK : hip_fail("ccfd_sym_kernel(stats)", e);
+  return e == hipSuccess ? VBHEM_OK : hip_fail(e, "ccfd_sym_kernel(stats)");
 }
 
 int vbhmm_ccfd_rho(const double *D_dev, int N, const double *dc, int C, int *rho_out_dev, void *stream) {
@@ -429,7 +419,7 @@ int vbhmm_ccfd_rho(const double *D_dev, int N, const double *dc, int C, int *rho
   hipLaunchKernelGGL(ccfd_rho_kernel, dim3((unsigned)N), dim3(kRowThreads), 0, static_cast<hipStream_t>(stream),
                      D_dev, N, cut, C, rho_out_dev);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VBHEM_OK : hip_fail("ccfd_rho_kernel", e);
+  return e == hipSuccess ? VBHEM_OK : hip_fail(e, "ccfd_rho_kernel");
 }
 
 int vbhmm_ccfd_delta(const double *D_dev, int N, const int *rank_dev, int C, double maxd, double *delta_out_dev,
@@ -442,7 +432,7 @@ int vbhmm_ccfd_delta(const double *D_dev, int N, const int *rank_dev, int C, dou
   hipLaunchKernelGGL(ccfd_delta_kernel, dim3((unsigned)N), dim3(kRowThreads), 0, static_cast<hipStream_t>(stream),
                      D_dev, N, rank_dev, C, maxd, delta_out_dev, nneigh_out_dev);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VBHEM_OK : hip_fail("ccfd_delta_kernel", e);
+  return e == hipSuccess ? VBHEM_OK : hip_fail(e, "ccfd_delta_kernel");
 }
 
 int vbhmm_ccfd_border(const double *D_dev, int N, double dc, const int *cl_dev, const int *rho_dev,
@@ -454,7 +444,7 @@ int vbhmm_ccfd_border(const double *D_dev, int N, double dc, const int *cl_dev, 
   hipLaunchKernelGGL(ccfd_border_kernel, dim3((unsigned)N), dim3(kRowThreads), 0, static_cast<hipStream_t>(stream),
                      D_dev, N, dc, cl_dev, rho_dev, rowmax_out_dev);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? VBHEM_OK : hip_fail("ccfd_border_kernel", e);
+  return e == hipSuccess ? VBHEM_OK : hip_fail(e, "ccfd_border_kernel");
 }
 
 }  // extern "C"

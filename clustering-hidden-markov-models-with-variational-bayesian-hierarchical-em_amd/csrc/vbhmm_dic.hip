@@ -222,7 +222,6 @@ hipError_t launch_sbp(const DicArgs &a, int SBP, dim3 grid, hipStream_t st) {
   return hipGetLastError();
 }
 
-size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 struct WsLayout {
   size_t blocks, partial, total;
@@ -246,8 +245,8 @@ int ws_layout(const vbhem_base_t *b, const vbhmm_dic_models_t *m, WsLayout &w) {
   w.blen = block_len(state_bucket(m->S), b->d);
   w.ntiles = (b->N + kTile - 1) / kTile;
   w.blocks = 0;
-  w.partial = align16((size_t)m->C * w.blen * sizeof(double));
-  w.total = w.partial + align16((size_t)w.ntiles * m->G * sizeof(double));
+  w.partial = align_up((size_t)m->C * w.blen * sizeof(double), 16);
+  w.total = w.partial + align_up((size_t)w.ntiles * m->G * sizeof(double), 16);
   return VBHEM_OK;
 }
 
@@ -290,14 +289,14 @@ int vbhmm_dic_loglik(const vbhem_base_t *b, const vbhmm_dic_models_t *m, int T, 
   const int SP = state_bucket(m->S), SBP = state_bucket(b->SB);
   hipLaunchKernelGGL(dic_prep_kernel, dim3((unsigned)((m->C + 63) / 64)), dim3(64), 0, st, a, SP);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("dic_prep_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "dic_prep_kernel");
   const dim3 grid((unsigned)w.ntiles, (unsigned)m->G);
   e = SP == 4 ? launch_sbp<4>(a, SBP, grid, st) : SP == 8 ? launch_sbp<8>(a, SBP, grid, st)
                                                           : launch_sbp<16>(a, SBP, grid, st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("dic_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "dic_kernel");
   hipLaunchKernelGGL(dic_reduce_kernel, dim3((unsigned)m->G), dim3(kThreads), 0, st, a);
   e = hipGetLastError();
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("dic_reduce_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "dic_reduce_kernel");
   return VBHEM_OK;
 }
 

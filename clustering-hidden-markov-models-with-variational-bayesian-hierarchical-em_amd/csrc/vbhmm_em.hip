@@ -192,7 +192,7 @@ int launch_chunks(EmArgs &a, int R, int KM, int chunk_runs, void *workspace_dev,
     else
       hipLaunchKernelGGL(vbhmm_em_kernel<8>, dim3(n), dim3(64), 0, st, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("vbhmm_em_kernel: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e, "vbhmm_em_kernel");
   }
   return VBHEM_OK;
 }

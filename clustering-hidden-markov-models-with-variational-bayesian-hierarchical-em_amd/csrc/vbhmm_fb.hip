@@ -214,7 +214,7 @@ int vbhmm_fb(const vbhmm_seqs_t *s, const vbhmm_params_t *q, double *logrho_dev,
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = q->K <= 4 ? launch_fbm<4>(a, st) : q->K <= 8 ? launch_fbm<8>(a, st)
                                                              : launch_fbm<16>(a, st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("vbhmm_fb_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "vbhmm_fb_kernel");
   return VBHEM_OK;
 }
 
@@ -231,7 +231,7 @@ int vbhmm_fb_host(int device, const vbhmm_seqs_t *sh, const vbhmm_params_t *qh, 
       return set_error(VBHEM_ERR_ARG, "sequence lengths must be in [0, maxT]");
   }
   hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   const size_t N = sh->N, K = qh->K, dim = sh->dim, T = sh->maxT, nx = (size_t)sh->offsets[N];
   const size_t n_in[] = {nx * dim, K * dim, K * dim * dim, K, K, K, K, K * K};
   const double *h_in[] = {sh->x, qh->m, qh->W, qh->v, qh->beta, qh->logLambdaTilde, qh->pz1, qh->A};
@@ -244,7 +244,7 @@ int vbhmm_fb_host(int device, const vbhmm_seqs_t *sh, const vbhmm_params_t *qh, 
   rc = VBHEM_OK;
   auto hf = [&rc](hipError_t err, const char *where) {
     if (err != hipSuccess && rc == VBHEM_OK)
-      rc = set_error(VBHEM_ERR_HIP, std::string(where) + ": " + hipGetErrorString(err));
+      rc = hip_fail(err, where);
   };
   for (int k = 0; k < 8 && rc == VBHEM_OK; ++k) {
     hf(hipMalloc(&d_in[k], std::max<size_t>(1, n_in[k]) * sizeof(double)), "hipMalloc(in)");

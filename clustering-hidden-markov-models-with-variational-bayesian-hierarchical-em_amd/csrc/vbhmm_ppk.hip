@@ -22,6 +22,7 @@
 
 #include "vbhem_estep.h"
 #include "vbhem_internal.h"
+#include "vbhmm_hmmset.h"
 #include "vbhmm_ppk.h"
 #include "vbhmm_ppk_pair.h"
 
@@ -32,8 +33,6 @@ using namespace ppk;
 
 constexpr int kGramThreads = 256;
 constexpr int kPrepThreads = 128;
-constexpr int kPrepHead = 8;  // doubles before the blocks: [0] two unsigned flags
-constexpr unsigned kNoFlag = 0xFFFFFFFFu;
 
 // HMMs per tile side: 4, or 2 where eight of the largest blocks would not leave LDS
 // for more than two workgroups per CU
@@ -43,30 +42,18 @@ struct Tile {
 };
 
 struct PrepArgs {
-  int H, KM, d, diag;
+  hmmset::Dims n;
   double rho, pad;
   Layout L;
-  const int *nstates;
-  const double *prior, *trans, *mean, *cov;
-  unsigned *flags;  // [0] first (h KM + k) not positive definite, [1] first h with a bad state count
-  double *blocks;
+  hmmset::Arrays a;
 };
 
 template <int DB>
 __global__ __launch_bounds__(kPrepThreads) void hmm_ppk_prep_kernel(const PrepArgs p) {
-  const long long g = (long long)blockIdx.x * kPrepThreads + threadIdx.x;
-  if (g >= (long long)p.H * p.KM) return;
-  const int h = (int)(g / p.KM), k = (int)(g % p.KM), KM = p.KM, d = p.d;
-  int K = p.nstates[h];
-  if (K < 1 || K > KM) {
-    atomicMin(&p.flags[1], (unsigned)h);
-    K = K < 1 ? 0 : KM;
-  }
-  const size_t cs = p.diag ? (size_t)d : (size_t)d * d;
-  const bool ok = prepare_state<DB>(p.L, p.blocks + (size_t)h * p.L.stride, k, K, d, p.diag != 0, p.rho,
-                                    p.pad, p.prior + (size_t)h * KM, p.trans + (size_t)h * KM * KM,
-                                    p.mean + (size_t)h * KM * d, p.cov + (size_t)h * KM * cs);
-  if (!ok) atomicMin(&p.flags[0], (unsigned)g);
+  hmmset::prep_lane(p.n, p.L.stride, p.a, kPrepThreads, [&](const hmmset::State &s) {
+    return prepare_state<DB>(p.L, s.blk, s.k, s.K, p.n.d, p.n.diag != 0, p.rho, p.pad, s.prior, s.trans, s.mean,
+                             s.cov);
+  });
 }
 
 struct GramArgs {
@@ -155,15 +142,6 @@ struct LaunchGram {
   }
 };
 
-int check_set(const vbhmm_score_hmms_t *m) {
-  if (!m) return set_error(VBHEM_ERR_ARG, "null HMM set");
-  if (m->H < 0 || m->KM < 1 || m->dim < 1 || (m->covmode != VBHEM_COV_DIAG && m->covmode != VBHEM_COV_FULL))
-    return set_error(VBHEM_ERR_ARG, "invalid HMM set (need H>=0, KM>=1, dim>=1, covmode diag or full)");
-  if (m->KM > kMaxStates || m->dim > kMaxDim)
-    return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_ppk: at most 16 states and 8 dimensions supported");
-  return VBHEM_OK;
-}
-
 }  // namespace
 }  // namespace vbhem
 
@@ -171,58 +149,35 @@ extern "C" {
 
 size_t vbhmm_ppk_prepared_bytes(const vbhmm_score_hmms_t *m) {
   using namespace vbhem;
-  if (!m || m->H < 0 || m->KM < 1 || m->KM > kMaxStates || m->dim < 1 || m->dim > kMaxDim) return 0;
-  return ((size_t)kPrepHead + (size_t)m->H * make_layout(m->KM, m->dim).stride) * sizeof(double);
+  return hmmset::prepared_bytes(m, [](int KM, int d) { return make_layout(KM, d).stride; });
 }
 
 int vbhmm_ppk_prepare(const vbhmm_score_hmms_t *m, double rho, double pad, void *prepared_dev,
                       size_t prepared_bytes, void *stream) {
   using namespace vbhem;
-  int rc = check_set(m);
+  const int rc = hmmset::check_set(m, "vbhmm_ppk");
   if (rc != VBHEM_OK) return rc;
   if (!(rho > 0.0) || !(pad >= 0.0) || std::isinf(rho) || std::isinf(pad))
     return set_error(VBHEM_ERR_ARG, "vbhmm_ppk: need a finite rho > 0 and pad >= 0");
-  const size_t need = vbhmm_ppk_prepared_bytes(m);
-  if (!prepared_dev || prepared_bytes < need)
-    return set_error(VBHEM_ERR_WORKSPACE, "prepared buffer too small: need " + std::to_string(need) + " bytes");
-  if (m->H == 0) return VBHEM_OK;
-  if (!m->nstates || !m->prior || !m->trans || !m->mean || !m->cov)
-    return set_error(VBHEM_ERR_ARG, "null HMM array");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PrepArgs a{};
-  a.H = m->H; a.KM = m->KM; a.d = m->dim; a.diag = m->covmode == VBHEM_COV_DIAG;
-  a.rho = rho; a.pad = pad;
-  a.L = make_layout(m->KM, m->dim);
-  a.nstates = m->nstates; a.prior = m->prior; a.trans = m->trans; a.mean = m->mean; a.cov = m->cov;
-  a.flags = static_cast<unsigned *>(prepared_dev);
-  a.blocks = static_cast<double *>(prepared_dev) + kPrepHead;
-  hipError_t e = hipMemsetAsync(prepared_dev, 0xFF, kPrepHead * sizeof(double), st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hipMemsetAsync(flags): ") + hipGetErrorString(e));
-  const unsigned grid = (unsigned)(((long long)m->H * m->KM + kPrepThreads - 1) / kPrepThreads);
-  switch (a.L.DB) {
-    case 2: hipLaunchKernelGGL(hmm_ppk_prep_kernel<2>, dim3(grid), dim3(kPrepThreads), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(hmm_ppk_prep_kernel<4>, dim3(grid), dim3(kPrepThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(hmm_ppk_prep_kernel<8>, dim3(grid), dim3(kPrepThreads), 0, st, a); break;
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_ppk_prep_kernel: ") + hipGetErrorString(e));
-  unsigned flags[2] = {kNoFlag, kNoFlag};
-  e = hipMemcpyAsync(flags, prepared_dev, sizeof(flags), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_ppk_prep_kernel (flags): ") + hipGetErrorString(e));
-  if (flags[1] != kNoFlag)
-    return set_error(VBHEM_ERR_ARG, "state count of HMM " + std::to_string(flags[1]) + " is outside [1, KM]");
-  if (flags[0] != kNoFlag)
-    return set_error(VBHEM_ERR_ARG, "regularised covariance of HMM " + std::to_string(flags[0] / m->KM) +
-                                        " state " + std::to_string(flags[0] % m->KM) + " is not positive definite");
-  return VBHEM_OK;
+  return hmmset::prepare(
+      m, prepared_dev, prepared_bytes, vbhmm_ppk_prepared_bytes(m), st, "hmm_ppk_prep_kernel",
+      "regularised covariance", [&](const hmmset::Dims &n, const hmmset::Arrays &arrays) {
+        const PrepArgs a{n, rho, pad, make_layout(n.KM, n.d), arrays};
+        const dim3 grid(hmmset::prep_grid(n, kPrepThreads)), block(kPrepThreads);
+        switch (a.L.DB) {
+          case 2: hipLaunchKernelGGL(hmm_ppk_prep_kernel<2>, grid, block, 0, st, a); break;
+          case 4: hipLaunchKernelGGL(hmm_ppk_prep_kernel<4>, grid, block, 0, st, a); break;
+          default: hipLaunchKernelGGL(hmm_ppk_prep_kernel<8>, grid, block, 0, st, a); break;
+        }
+      });
 }
 
 int vbhmm_ppk_gram(const vbhmm_score_hmms_t *ma, const void *prepared_a, const vbhmm_score_hmms_t *mb,
                    const void *prepared_b, int T, int mode, double *out_dev, void *stream) {
   using namespace vbhem;
-  int rc = check_set(ma);
-  if (rc == VBHEM_OK) rc = check_set(mb);
+  int rc = hmmset::check_set(ma, "vbhmm_ppk");
+  if (rc == VBHEM_OK) rc = hmmset::check_set(mb, "vbhmm_ppk");
   if (rc != VBHEM_OK) return rc;
   if (ma->dim != mb->dim) return set_error(VBHEM_ERR_ARG, "vbhmm_ppk_gram: the two sets differ in dimension");
   if (T < 1) return set_error(VBHEM_ERR_ARG, "vbhmm_ppk_gram: T must be >= 1");
@@ -238,14 +193,14 @@ int vbhmm_ppk_gram(const vbhmm_score_hmms_t *ma, const void *prepared_a, const v
   a.Ha = ma->H; a.Hb = mb->H; a.d = ma->dim; a.T = T; a.mode = mode;
   a.La = make_layout(ma->KM, ma->dim);
   a.Lb = make_layout(mb->KM, mb->dim);
-  a.blocks_a = static_cast<const double *>(prepared_a) + kPrepHead;
-  a.blocks_b = static_cast<const double *>(prepared_b) + kPrepHead;
+  a.blocks_a = hmmset::blocks(prepared_a);
+  a.blocks_b = hmmset::blocks(prepared_b);
   a.out = out_dev;
   const int KM = ma->KM > mb->KM ? ma->KM : mb->KM;
   const hipError_t e = dispatch(KM, ma->dim, LaunchGram{a, static_cast<hipStream_t>(stream)});
   if (e == hipErrorInvalidConfiguration)
     return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_ppk_gram: too many tiles of HMM pairs; split the sets");
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_ppk_gram_kernel: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hmm_ppk_gram_kernel");
   return VBHEM_OK;
 }
 

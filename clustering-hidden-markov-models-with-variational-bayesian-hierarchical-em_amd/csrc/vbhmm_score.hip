@@ -18,6 +18,7 @@
 
 #include "vbhem_estep.h"
 #include "vbhem_internal.h"
+#include "vbhmm_hmmset.h"
 #include "vbhmm_score.h"
 #include "vbhmm_score_pair.h"
 
@@ -28,33 +29,18 @@ using namespace score;
 
 constexpr int kScoreThreads = 128;
 constexpr int kPrepThreads = 256;
-constexpr int kPrepHead = 8;  // doubles before the blocks: [0] two unsigned flags
-constexpr unsigned kNoFlag = 0xFFFFFFFFu;
 enum ScoreMode : int { kScoreLL = 0, kScoreViterbi = 1 };
 
 struct PrepArgs {
-  int H, KM, d, diag;
+  hmmset::Dims n;
   Layout L;
-  const int *nstates;
-  const double *prior, *trans, *mean, *cov;
-  unsigned *flags;  // [0] first (h KM + k) not positive definite, [1] first h with a bad state count
-  double *blocks;
+  hmmset::Arrays a;
 };
 
 __global__ __launch_bounds__(kPrepThreads) void hmm_score_prep_kernel(const PrepArgs p) {
-  const long long g = (long long)blockIdx.x * kPrepThreads + threadIdx.x;
-  if (g >= (long long)p.H * p.KM) return;
-  const int h = (int)(g / p.KM), k = (int)(g % p.KM), KM = p.KM, d = p.d;
-  int K = p.nstates[h];
-  if (K < 1 || K > KM) {
-    atomicMin(&p.flags[1], (unsigned)h);
-    K = K < 1 ? 0 : KM;
-  }
-  const size_t cs = p.diag ? (size_t)d : (size_t)d * d;
-  const bool ok = prepare_state(p.L, p.blocks + (size_t)h * p.L.stride, k, K, d, p.diag != 0,
-                                p.prior + (size_t)h * KM, p.trans + (size_t)h * KM * KM,
-                                p.mean + (size_t)h * KM * d, p.cov + (size_t)h * KM * cs);
-  if (!ok) atomicMin(&p.flags[0], (unsigned)g);
+  hmmset::prep_lane(p.n, p.L.stride, p.a, kPrepThreads, [&](const hmmset::State &s) {
+    return prepare_state(p.L, s.blk, s.k, s.K, p.n.d, p.n.diag != 0, s.prior, s.trans, s.mean, s.cov);
+  });
 }
 
 struct ScoreArgs {
@@ -74,7 +60,7 @@ __global__ __launch_bounds__(kScoreThreads) void hmm_score_kernel(const ScoreArg
   __shared__ double sh[BlockLen<KB, DB>::value];
   const int h = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
   const double *blk = p.blocks + (size_t)h * p.L.stride;
-  for (int q = threadIdx.x; q < p.L.stride; q += kScoreThreads) sh[q] = blk[q];
+  hmmset::stage_block(sh, blk, p.L.stride, kScoreThreads);
   __syncthreads();
   const int n = tile * kScoreThreads + threadIdx.x;
   if (n >= p.N) return;
@@ -104,20 +90,11 @@ struct Launch {
   }
 };
 
-int check_hmms(const vbhmm_score_hmms_t *m) {
-  if (!m) return set_error(VBHEM_ERR_ARG, "null HMM set");
-  if (m->H < 0 || m->KM < 1 || m->dim < 1 ||
-      (m->covmode != VBHEM_COV_DIAG && m->covmode != VBHEM_COV_FULL))
-    return set_error(VBHEM_ERR_ARG, "invalid HMM set (need H>=0, KM>=1, dim>=1, covmode diag or full)");
-  if (m->KM > kMaxStates || m->dim > kMaxDim)
-    return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_score: at most 16 states and 8 dimensions supported");
-  return VBHEM_OK;
-}
-
-int check_seqs(const vbhmm_score_hmms_t *m, const vbhmm_seqs_t *s, long long &tiles) {
-  if (!s) return set_error(VBHEM_ERR_ARG, "null sequences");
-  if (s->N < 0 || s->dim != m->dim) return set_error(VBHEM_ERR_ARG, "invalid sequences (need N>=0, the HMMs' dim)");
-  if (s->N > 0 && (!s->offsets || !s->x)) return set_error(VBHEM_ERR_ARG, "null sequence array");
+// the set, the sequences and the (HMM, sequence tile) grid of a scoring call
+int check_call(const vbhmm_score_hmms_t *m, const vbhmm_seqs_t *s, long long &tiles) {
+  int rc = hmmset::check_set(m, "vbhmm_score");
+  if (rc == VBHEM_OK) rc = hmmset::check_seqs(m, s);
+  if (rc != VBHEM_OK) return rc;
   tiles = ((long long)s->N + kScoreThreads - 1) / kScoreThreads;
   if (tiles * m->H > INT_MAX)
     return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_score: too many (HMM, sequence tile) workgroups; split the HMM set");
@@ -129,7 +106,7 @@ ScoreArgs score_args(const vbhmm_score_hmms_t *m, const void *prepared, const vb
   ScoreArgs a{};
   a.H = m->H; a.N = s->N; a.d = m->dim; a.diag = m->covmode == VBHEM_COV_DIAG; a.tiles = (int)tiles;
   a.L = make_layout(m->KM, m->dim);
-  a.blocks = static_cast<const double *>(prepared) + kPrepHead;
+  a.blocks = hmmset::blocks(prepared);
   a.offsets = s->offsets; a.x = s->x; a.loglik = loglik;
   return a;
 }
@@ -141,44 +118,22 @@ extern "C" {
 
 size_t vbhmm_score_prepared_bytes(const vbhmm_score_hmms_t *m) {
   using namespace vbhem;
-  if (!m || m->H < 0 || m->KM < 1 || m->KM > kMaxStates || m->dim < 1 || m->dim > kMaxDim) return 0;
-  return ((size_t)kPrepHead + (size_t)m->H * make_layout(m->KM, m->dim).stride) * sizeof(double);
+  return hmmset::prepared_bytes(m, [](int KM, int d) { return make_layout(KM, d).stride; });
 }
 
 int vbhmm_score_prepare(const vbhmm_score_hmms_t *m, void *prepared_dev, size_t prepared_bytes,
                         void *stream) {
   using namespace vbhem;
-  int rc = check_hmms(m);
+  const int rc = hmmset::check_set(m, "vbhmm_score");
   if (rc != VBHEM_OK) return rc;
-  const size_t need = vbhmm_score_prepared_bytes(m);
-  if (!prepared_dev || prepared_bytes < need)
-    return set_error(VBHEM_ERR_WORKSPACE, "prepared buffer too small: need " + std::to_string(need) + " bytes");
-  if (m->H == 0) return VBHEM_OK;
-  if (!m->nstates || !m->prior || !m->trans || !m->mean || !m->cov)
-    return set_error(VBHEM_ERR_ARG, "null HMM array");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PrepArgs a{};
-  a.H = m->H; a.KM = m->KM; a.d = m->dim; a.diag = m->covmode == VBHEM_COV_DIAG;
-  a.L = make_layout(m->KM, m->dim);
-  a.nstates = m->nstates; a.prior = m->prior; a.trans = m->trans; a.mean = m->mean; a.cov = m->cov;
-  a.flags = static_cast<unsigned *>(prepared_dev);
-  a.blocks = static_cast<double *>(prepared_dev) + kPrepHead;
-  hipError_t e = hipMemsetAsync(prepared_dev, 0xFF, kPrepHead * sizeof(double), st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hipMemsetAsync(flags): ") + hipGetErrorString(e));
-  const unsigned grid = (unsigned)(((long long)m->H * m->KM + kPrepThreads - 1) / kPrepThreads);
-  hipLaunchKernelGGL(hmm_score_prep_kernel, dim3(grid), dim3(kPrepThreads), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_score_prep_kernel: ") + hipGetErrorString(e));
-  unsigned flags[2] = {kNoFlag, kNoFlag};
-  e = hipMemcpyAsync(flags, prepared_dev, sizeof(flags), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_score_prep_kernel (flags): ") + hipGetErrorString(e));
-  if (flags[1] != kNoFlag)
-    return set_error(VBHEM_ERR_ARG, "state count of HMM " + std::to_string(flags[1]) + " is outside [1, KM]");
-  if (flags[0] != kNoFlag)
-    return set_error(VBHEM_ERR_ARG, "covariance of HMM " + std::to_string(flags[0] / m->KM) + " state " +
-                                        std::to_string(flags[0] % m->KM) + " is not positive definite");
-  return VBHEM_OK;
+  return hmmset::prepare(m, prepared_dev, prepared_bytes, vbhmm_score_prepared_bytes(m), st,
+                         "hmm_score_prep_kernel", "covariance",
+                         [&](const hmmset::Dims &n, const hmmset::Arrays &arrays) {
+                           const PrepArgs a{n, make_layout(n.KM, n.d), arrays};
+                           hipLaunchKernelGGL(hmm_score_prep_kernel, dim3(hmmset::prep_grid(n, kPrepThreads)),
+                                              dim3(kPrepThreads), 0, st, a);
+                         });
 }
 
 size_t vbhmm_score_workspace_bytes(const vbhmm_score_hmms_t *m, long long total_steps) {
@@ -190,15 +145,14 @@ size_t vbhmm_score_workspace_bytes(const vbhmm_score_hmms_t *m, long long total_
 int vbhmm_score_ll(const vbhmm_score_hmms_t *m, const void *prepared_dev, const vbhmm_seqs_t *s,
                    double *loglik_dev, void *stream) {
   using namespace vbhem;
-  int rc = check_hmms(m);
   long long tiles = 0;
-  if (rc == VBHEM_OK) rc = check_seqs(m, s, tiles);
+  const int rc = check_call(m, s, tiles);
   if (rc != VBHEM_OK) return rc;
   if (m->H == 0 || s->N == 0) return VBHEM_OK;
   if (!prepared_dev || !loglik_dev) return set_error(VBHEM_ERR_ARG, "null prepared buffer or output");
   const ScoreArgs a = score_args(m, prepared_dev, s, tiles, loglik_dev);
   const hipError_t e = dispatch(m->KM, m->dim, Launch<kScoreLL>{a, static_cast<hipStream_t>(stream)});
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_score_kernel(ll): ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hmm_score_kernel(ll)");
   return VBHEM_OK;
 }
 
@@ -206,9 +160,8 @@ int vbhmm_score_viterbi(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
                         long long total_steps, int *path_dev, double *loglik_dev, void *workspace_dev,
                         size_t workspace_bytes, void *stream) {
   using namespace vbhem;
-  int rc = check_hmms(m);
   long long tiles = 0;
-  if (rc == VBHEM_OK) rc = check_seqs(m, s, tiles);
+  const int rc = check_call(m, s, tiles);
   if (rc != VBHEM_OK) return rc;
   if (total_steps < 0) return set_error(VBHEM_ERR_ARG, "total_steps must be >= 0");
   if (m->H == 0 || s->N == 0) return VBHEM_OK;
@@ -223,7 +176,7 @@ int vbhmm_score_viterbi(const vbhmm_score_hmms_t *m, const void *prepared_dev, c
   a.path = path_dev;
   a.bp = static_cast<unsigned char *>(workspace_dev);
   const hipError_t e = dispatch(m->KM, m->dim, Launch<kScoreViterbi>{a, static_cast<hipStream_t>(stream)});
-  if (e != hipSuccess) return set_error(VBHEM_ERR_HIP, std::string("hmm_score_kernel(viterbi): ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hmm_score_kernel(viterbi)");
   return VBHEM_OK;
 }
 

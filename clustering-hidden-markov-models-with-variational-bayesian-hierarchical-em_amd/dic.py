@@ -112,10 +112,10 @@ def _loglik_fused(base: BaseSet, pk: dict, T: int, device, want_pairs: bool):
                           *[_capi.ptr(dev[k]) for k in ("model_off", "nstates_r", "logw", "scale",
                                                         "logA", "logPi", "m", "P", "c")])
     nb = int(lib.vbhmm_dic_workspace_bytes(ctypes.byref(bt), ctypes.byref(mt), int(T)))
-    ws = torch.empty((max(nb, 16),), dtype=torch.uint8, device=dv)
+    ws = _capi.workspace(nb, dv, align=16)
     LL = torch.empty((pk["G"],), dtype=torch.float64, device=dv)
     Lp = torch.empty((base.N, pk["C"]), dtype=torch.float64, device=dv) if want_pairs else None
-    st = ctypes.c_void_p(torch.cuda.current_stream(dv).cuda_stream)
+    st = _capi.stream(dv)
     rc = lib.vbhmm_dic_loglik(ctypes.byref(bt), ctypes.byref(mt), int(T), _capi.ptr(LL),
                               _capi.ptr(Lp), _capi.ptr(ws), ws.numel(), st)
     if rc == VBHEM_ERR_UNSUPPORTED:

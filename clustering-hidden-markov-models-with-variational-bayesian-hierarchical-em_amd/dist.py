@@ -125,7 +125,7 @@ class RcclComm:
         from . import _capi
         if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
             raise ValueError("RcclComm.allreduce: a contiguous fp64 device tensor")
-        st = torch.cuda.current_stream(t.device).cuda_stream
+        st = _capi.stream(t.device)
         _capi.check(self._lib.vbhem_rccl_allreduce_sum(self.handle, _capi.ptr(t), t.numel(), st),
                     "vbhem_rccl_allreduce_sum")
 
@@ -135,7 +135,7 @@ class RcclComm:
         from . import _capi
         if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
             raise ValueError("RcclComm.allreduce_to: a contiguous fp64 device tensor")
-        st = torch.cuda.current_stream(t.device).cuda_stream
+        st = _capi.stream(t.device)
         _capi.check(self._lib.vbhem_rccl_allreduce_to(self.handle, _capi.ptr(t), t.numel(),
                                                       ctypes.c_void_p(out_dev), st),
                     "vbhem_rccl_allreduce_to")

@@ -94,7 +94,7 @@ class EStepEngine:
         self.logOmega.copy_(src)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _capi.stream(self.device)
 
     # -- MEX-equivalent per-pair outputs ------------------------------------
     def pairs(self, want_tnu: bool = False, smooth=None) -> dict:
@@ -116,7 +116,7 @@ class EStepEngine:
         if self._ws_pairs is None:
             nb = int(self.lib.vbhem_pairs_workspace_bytes(ctypes.byref(self._bt),
                                                           ctypes.byref(self._ct), self.T))
-            self._ws_pairs = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dv)
+            self._ws_pairs = _capi.workspace(nb, dv)
         outs = (_capi.ptr(out["LL_elbo"]), _capi.ptr(out["sum_nu_1"]), _capi.ptr(out["emit_pr"]),
                 _capi.ptr(out["emit_mu"]), _capi.ptr(out["emit_Mu"]), _capi.ptr(out["sum_xi"]),
                 _capi.ptr(out.get("sum_t_nu")), _capi.ptr(self._ws_pairs), self._ws_pairs.numel(),
@@ -182,7 +182,7 @@ class EStepEngine:
         if self._ws_fused is None:
             nb = int(self.lib.vbhem_fused_trials_workspace_bytes(
                 ctypes.byref(self._bt), ctypes.byref(self._ct), self.trials, self.T))
-            self._ws_fused = torch.empty((max(nb, 1),), dtype=torch.uint8, device=self.device)
+            self._ws_fused = _capi.workspace(nb, self.device)
         res = self.stats if out is None else out
         sp = _capi.ptr(self.stats) if out is None else self._out_ptr(out)
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -220,7 +220,7 @@ class EStepEngine:
         if self._ws_fused is None:
             nb = int(self.lib.vhem_fused_trials_workspace_bytes(
                 ctypes.byref(self._bt), ctypes.byref(self._ct), self.trials, self.T))
-            self._ws_fused = torch.empty((max(nb, 1),), dtype=torch.uint8, device=self.device)
+            self._ws_fused = _capi.workspace(nb, self.device)
         res = self.stats if out is None else out
         sp = _capi.ptr(self.stats) if out is None else self._out_ptr(out)
         head = (ctypes.byref(self._bt), ctypes.byref(self._ct))

@@ -156,8 +156,6 @@ def hmms_to_h3m_hem_device(hmms: List[Optional[dict]], covmode: int = COV_FULL,
     arrays of the raw variational counts, point estimates, means and covariances
     here, uploaded once, and the digamma / exp / inflation / weights run as a
     kernel; the BaseSet comes back on ``device``."""
-    import ctypes
-
     from . import _capi
     nin = next(len(h["pdf"][0]["mean"]) for h in hmms if h is not None)
     N, d = len(hmms), nin
@@ -193,7 +191,7 @@ def hmms_to_h3m_hem_device(hmms: List[Optional[dict]], covmode: int = COV_FULL,
                                   dtype=torch.float64, device=dev),
                omega=torch.empty((N,), dtype=torch.float64, device=dev))
     ws = torch.zeros((1,), dtype=torch.int32, device=dev)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _capi.stream(dev)
     p = _capi.ptr
     _capi.check(_capi.lib().vbhem_hmms_to_h3m(
         N, SB, d, int(covmode), 1 if use_post else 0, p(ins["ns"]), p(ins["al"]), p(ins["ep"]),

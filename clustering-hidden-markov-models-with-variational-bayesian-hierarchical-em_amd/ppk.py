@@ -22,14 +22,14 @@ import torch
 
 from . import _capi
 from .h3m import BaseSet, kmeans_pp
-from .score import _as_list, pack_hmms
+from .score import PreparedSet, _as_list
 
 F64 = torch.float64
 MODE_RECT, MODE_SYM, MODE_DIAG = 0, 1, 2  # include/vbhmm_ppk.h
 KMEANS_MAX_ITER = 200                     # SpectralClustering.m:89-90
 
 
-class PpkSet:
+class PpkSet(PreparedSet):
     """H point HMMs prepared for the probability product kernel (regularised
     covariances ``cov + pad`` on every entry plus ``1e-5 trace I``, their
     log-determinants, ``prior ** rho``, ``trans ** rho``) and resident on ``device``.
@@ -40,39 +40,13 @@ class PpkSet:
     the HMM and the state."""
 
     def __init__(self, hmms, rho: float = 0.5, pad: float = 0.45, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PpkSet lives on a GPU (HIP); there is no CPU path")
-        self.lib = _capi.lib()
+        self._load(hmms, device)
         self.rho, self.pad = float(rho), float(pad)
-        dv = self.device
-        if isinstance(hmms, BaseSet):
-            b = hmms.to(dv)
-            self.nstates = b.nstates.to(torch.int32).contiguous()
-            self.prior, self.trans = b.prior.to(F64).contiguous(), b.A.to(F64).contiguous()
-            self.mean, self.cov = b.centres.to(F64).contiguous(), b.covars.to(F64).contiguous()
-            self.covmode = int(b.covmode)
-        else:
-            packed = pack_hmms(_as_list(hmms))
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dv)
-            self.nstates, self.prior, self.trans = t(packed["nstates"]), t(packed["prior"]), t(packed["trans"])
-            self.mean, self.cov, self.covmode = t(packed["mean"]), t(packed["cov"]), packed["covmode"]
-        self.H, self.KM, self.dim = (int(s) for s in self.mean.shape)
-        self._desc = _capi.ScoreHmmsT(self.H, self.KM, self.dim, self.covmode, _capi.ptr(self.nstates),
-                                      _capi.ptr(self.prior), _capi.ptr(self.trans),
-                                      _capi.ptr(self.mean), _capi.ptr(self.cov))
-        nb = int(self.lib.vbhmm_ppk_prepared_bytes(ctypes.byref(self._desc)))
-        self.prepared = torch.empty((max(nb, 8) // 8,), dtype=F64, device=dv)
+        self._alloc_prepared(self.lib.vbhmm_ppk_prepared_bytes)
         _capi.check(self.lib.vbhmm_ppk_prepare(ctypes.byref(self._desc), self.rho, self.pad,
                                                _capi.ptr(self.prepared), self.prepared.numel() * 8,
                                                self._stream()),
                     "vbhmm_ppk_prepare")
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def desc(self) -> "_capi.ScoreHmmsT":
-        return self._desc
 
 
 def _gram(a: PpkSet, b: PpkSet, T: int, mode: int) -> torch.Tensor:

@@ -84,18 +84,16 @@ def _as_list(data) -> list:
     return list(data) if isinstance(data, (list, tuple)) else [data]
 
 
-class HmmSet:
-    """H point HMMs, prepared (Cholesky factors inverted, log-normalisers) and
-    resident on ``device``.  ``hmms``: a list of HMM dicts (``prior``, ``trans``,
-    ``pdf[{mean, cov}]``; ragged state counts; all of one dimension), or a packed
-    :class:`BaseSet`, whose device arrays are read where they are.  At most 16
-    states and 8 dimensions.  A covariance that is not positive definite raises
-    :class:`_capi.VbhemError` naming the HMM and the state."""
+class PreparedSet:
+    """What :class:`HmmSet` and :class:`ppk.PpkSet` share: H point HMMs as the five
+    device arrays of include/vbhmm_score.h, their descriptor, and a prepared buffer
+    sized by the subclass's ``*_prepared_bytes``.  The subclass fills the buffer."""
 
-    def __init__(self, hmms, device="cuda"):
+    def _load(self, hmms, device):
+        """``hmms`` (HMM dicts or a :class:`BaseSet`) onto ``device``; the descriptor."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError("HmmSet lives on a GPU (HIP); there is no CPU path")
+            raise ValueError(f"{type(self).__name__} lives on a GPU (HIP); there is no CPU path")
         self.lib = _capi.lib()
         dv = self.device
         if isinstance(hmms, BaseSet):
@@ -113,19 +111,34 @@ class HmmSet:
         self._desc = _capi.ScoreHmmsT(self.H, self.KM, self.dim, self.covmode, _capi.ptr(self.nstates),
                                       _capi.ptr(self.prior), _capi.ptr(self.trans),
                                       _capi.ptr(self.mean), _capi.ptr(self.cov))
-        if self.KM > MAX_STATES or self.dim > MAX_DIM:
-            raise ValueError(f"at most {MAX_STATES} states and {MAX_DIM} dimensions are supported")
-        nb = int(self.lib.vbhmm_score_prepared_bytes(ctypes.byref(self._desc)))
-        self.prepared = torch.empty((max(nb, 8) // 8,), dtype=F64, device=dv)
-        _capi.check(self.lib.vbhmm_score_prepare(ctypes.byref(self._desc), _capi.ptr(self.prepared),
-                                                 self.prepared.numel() * 8, self._stream()),
-                    "vbhmm_score_prepare")
+
+    def _alloc_prepared(self, prepared_bytes):
+        nb = int(prepared_bytes(ctypes.byref(self._desc)))
+        self.prepared = torch.empty((max(nb, 8) // 8,), dtype=F64, device=self.device)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _capi.stream(self.device)
 
     def desc(self) -> "_capi.ScoreHmmsT":
         return self._desc
+
+
+class HmmSet(PreparedSet):
+    """H point HMMs, prepared (Cholesky factors inverted, log-normalisers) and
+    resident on ``device``.  ``hmms``: a list of HMM dicts (``prior``, ``trans``,
+    ``pdf[{mean, cov}]``; ragged state counts; all of one dimension), or a packed
+    :class:`BaseSet`, whose device arrays are read where they are.  At most 16
+    states and 8 dimensions.  A covariance that is not positive definite raises
+    :class:`_capi.VbhemError` naming the HMM and the state."""
+
+    def __init__(self, hmms, device="cuda"):
+        self._load(hmms, device)
+        if self.KM > MAX_STATES or self.dim > MAX_DIM:
+            raise ValueError(f"at most {MAX_STATES} states and {MAX_DIM} dimensions are supported")
+        self._alloc_prepared(self.lib.vbhmm_score_prepared_bytes)
+        _capi.check(self.lib.vbhmm_score_prepare(ctypes.byref(self._desc), _capi.ptr(self.prepared),
+                                                 self.prepared.numel() * 8, self._stream()),
+                    "vbhmm_score_prepare")
 
 
 def pack_hmms(hmms: List[dict]) -> dict:
@@ -185,7 +198,7 @@ def viterbi(hset: HmmSet, batch):
     path = torch.zeros((hset.H, total), dtype=torch.int32, device=hset.device)
     ll = torch.empty((hset.H, sb.N), dtype=F64, device=hset.device)
     nb = int(hset.lib.vbhmm_score_workspace_bytes(ctypes.byref(hset.desc()), total))
-    ws = torch.empty((max(nb, 16),), dtype=torch.uint8, device=hset.device)
+    ws = _capi.workspace(nb, hset.device, align=16)
     sd = sb.desc()
     _capi.check(hset.lib.vbhmm_score_viterbi(ctypes.byref(hset.desc()), _capi.ptr(hset.prepared),
                                              ctypes.byref(sd), total, _capi.ptr(path), _capi.ptr(ll),

@@ -116,8 +116,8 @@ def vbhmm_fb(data, varpar: dict, device="cuda", pre: Optional[dict] = None,
     phi = torch.empty((max(N, 1),), dtype=F64, device=dev)
     sd = sb.desc()
     nb = int(lib.vbhmm_fb_workspace_bytes(ctypes.byref(sd), K))
-    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ws = _capi.workspace(nb, dev)
+    stream = _capi.stream(dev)
     rc = lib.vbhmm_fb(ctypes.byref(sd), ctypes.byref(par), _capi.ptr(logrho), _capi.ptr(gamma),
                       _capi.ptr(xi), _capi.ptr(phi), _capi.ptr(ws), ws.numel(), stream)
     _capi.check(rc, "vbhmm_fb")

@@ -498,8 +498,8 @@ def vbhmm_em_gamma(subjects, items, chunk_runs: int = 0) -> list:
     status = torch.zeros(len(items), dtype=torch.int32, device=dev)
     sd = subjects.desc()
     nb = int(lib.vbhmm_em_batch_workspace_bytes(ctypes.byref(sd), len(items), KM, chunk_runs))
-    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ws = _capi.workspace(nb, dev)
+    stream = _capi.stream(dev)
     _capi.check(lib.vbhmm_em_gamma(ctypes.byref(sd), ctypes.byref(rn), _capi.ptr(gam), _capi.ptr(d_rows),
                                    _capi.ptr(status), chunk_runs, _capi.ptr(ws), ws.numel(), stream),
                 "vbhmm_em_gamma")
@@ -588,8 +588,8 @@ def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = Fals
     o_LLs = torch.zeros((R, max_iter), dtype=f64, device=dev) if keep_LLs else None
     sd = subjects.desc()
     nb = int(lib.vbhmm_em_batch_workspace_bytes(ctypes.byref(sd), R, KM, int(chunk_runs)))
-    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ws = _capi.workspace(nb, dev)
+    stream = _capi.stream(dev)
     t1 = time.perf_counter()
     _capi.check(lib.vbhmm_em_batch(ctypes.byref(sd), ctypes.byref(rn), ctypes.byref(hy), ctypes.byref(bo),
                                    _capi.ptr(o_post), _capi.ptr(o_est), _capi.ptr(o_stats), _capi.ptr(o_LL),

@@ -9,6 +9,8 @@
 #include <cmath>
 #include <vector>
 
+#include "device_pool.h"
+#include "host_prepare.h"
 #include "vbhmm_ccfd.h"
 #include "vbhmm_ccfd_row.h"
 #include "vbhmm_score_pair.h"
@@ -59,24 +61,7 @@ struct HostDistance {
   }
 };
 
-// device copies of host arrays, freed together
-struct Pool {
-  std::vector<void *> p;
-  hipError_t e = hipSuccess;
-  void *put(const void *host, size_t bytes) {
-    void *q = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&q, bytes + 16);
-    if (e == hipSuccess && bytes && host) e = hipMemcpy(q, host, bytes, hipMemcpyHostToDevice);
-    p.push_back(q);
-    return q;
-  }
-  void get(void *host, const void *dev, size_t bytes) {
-    if (e == hipSuccess && bytes) e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-  }
-  ~Pool() {
-    for (void *q : p) (void)hipFree(q);
-  }
-};
+using checklib::Pool;
 
 }  // namespace
 
@@ -87,17 +72,11 @@ long long ccfdcheck_distance_host(int H, int KM, int d, int covmode, const int *
                                   const double *trans, const double *mean, const double *cov, int N,
                                   const int *offsets, const double *x, const int *seg, double *D) {
   const Layout L = make_layout(KM, d);
-  const bool diag = covmode == VBHEM_COV_DIAG;
-  const size_t cs = diag ? (size_t)d : (size_t)d * d;
-  std::vector<double> blocks((size_t)H * L.stride, 0.0);
-  for (int h = 0; h < H; ++h)
-    for (int k = 0; k < KM; ++k)
-      if (!prepare_state(L, blocks.data() + (size_t)h * L.stride, k, nstates[h], d, diag,
-                         prior + (size_t)h * KM, trans + (size_t)h * KM * KM, mean + (size_t)h * KM * d,
-                         cov + (size_t)h * KM * cs))
-        return 1 + (long long)h * KM + k;
+  std::vector<double> blocks;
+  const long long bad = checklib::host_prepare(L, H, KM, d, covmode, nstates, prior, trans, mean, cov, blocks);
+  if (bad) return bad;
   (void)N;
-  return dispatch(KM, d, HostDistance{L, blocks, H, d, diag, offsets, seg, x, D});
+  return dispatch(KM, d, HostDistance{L, blocks, H, d, covmode == VBHEM_COV_DIAG, offsets, seg, x, D});
 }
 
 // The same through vbhmm_score_prepare / vbhmm_ccfd_distance on device 0; rowmin and

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <vector>
 
+#include "device_pool.h"
 #include "vbhmm_dic.h"
 #include "vbhmm_dic_pair.h"
 
@@ -15,23 +16,7 @@ namespace {
 
 using namespace vbhem::dic;
 
-struct Pool {
-  std::vector<void *> p;
-  hipError_t e = hipSuccess;
-  void *put(const void *host, size_t bytes) {
-    void *q = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&q, bytes + 16);
-    if (e == hipSuccess && bytes && host) e = hipMemcpy(q, host, bytes, hipMemcpyHostToDevice);
-    p.push_back(q);
-    return q;
-  }
-  void get(void *host, const void *dev, size_t bytes) {
-    if (e == hipSuccess && bytes) e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-  }
-  ~Pool() {
-    for (void *q : p) (void)hipFree(q);
-  }
-};
+using checklib::Pool;
 
 template <int SP>
 void host_pairs(int N, int SB, int d, const int *nstates, const double *prior, const double *A,

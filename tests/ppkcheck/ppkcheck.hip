@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "device_pool.h"
 #include "vbhmm_ppk.h"
 #include "vbhmm_ppk_pair.h"
 
@@ -67,33 +68,23 @@ struct HostGram {
 };
 
 struct DevSet {
-  void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  void *prep = nullptr;
   vbhmm_score_hmms_t m{};
+  void *prep = nullptr;
   size_t pb = 0;
 };
 
-hipError_t upload(const Set &s, int d, int covmode, DevSet &v) {
+DevSet upload(const Set &s, int d, int covmode, checklib::Pool &pool) {
   const size_t cs = covmode == VBHEM_COV_DIAG ? (size_t)d : (size_t)d * d;
-  const size_t bytes[] = {(size_t)s.H * sizeof(int), (size_t)s.H * s.KM * 8, (size_t)s.H * s.KM * s.KM * 8,
-                          (size_t)s.H * s.KM * d * 8, (size_t)s.H * s.KM * cs * 8};
-  const void *host[] = {s.nstates, s.prior, s.trans, s.mean, s.cov};
-  hipError_t e = hipSuccess;
-  for (int q = 0; q < 5 && e == hipSuccess; ++q) {
-    e = hipMalloc(&v.p[q], bytes[q] + 8);
-    if (e == hipSuccess && bytes[q]) e = hipMemcpy(v.p[q], host[q], bytes[q], hipMemcpyHostToDevice);
-  }
-  v.m = {s.H, s.KM, d, covmode, static_cast<const int *>(v.p[0]), static_cast<const double *>(v.p[1]),
-         static_cast<const double *>(v.p[2]), static_cast<const double *>(v.p[3]),
-         static_cast<const double *>(v.p[4])};
+  DevSet v;
+  v.m = {s.H, s.KM, d, covmode,
+         static_cast<const int *>(pool.put(s.nstates, (size_t)s.H * sizeof(int))),
+         static_cast<const double *>(pool.put(s.prior, (size_t)s.H * s.KM * 8)),
+         static_cast<const double *>(pool.put(s.trans, (size_t)s.H * s.KM * s.KM * 8)),
+         static_cast<const double *>(pool.put(s.mean, (size_t)s.H * s.KM * d * 8)),
+         static_cast<const double *>(pool.put(s.cov, (size_t)s.H * s.KM * cs * 8))};
   v.pb = vbhmm_ppk_prepared_bytes(&v.m);
-  if (e == hipSuccess) e = hipMalloc(&v.prep, v.pb + 8);
-  return e;
-}
-
-void release(DevSet &v) {
-  for (void *q : v.p) (void)hipFree(q);
-  (void)hipFree(v.prep);
+  v.prep = pool.put(nullptr, v.pb);
+  return v;
 }
 
 }  // namespace
@@ -130,25 +121,17 @@ int ppkcheck_device(int d, int covmode, double rho, double pad, int T, int mode,
   const Set sb{Hb, KMb, nstates_b, prior_b, trans_b, mean_b, cov_b};
   const bool sym = mode == VBHMM_PPK_SYM;
   const size_t out_bytes = (mode == VBHMM_PPK_DIAG ? (size_t)Ha : (size_t)Ha * Hb) * 8;
-  DevSet da, db;
-  void *dout = nullptr;
-  int rc = 0;
-  hipError_t e = upload(sa, d, covmode, da);
-  if (e == hipSuccess && !sym) e = upload(sb, d, covmode, db);
-  if (e == hipSuccess) e = hipMalloc(&dout, out_bytes + 8);
-  if (e == hipSuccess) {
-    rc = vbhmm_ppk_prepare(&da.m, rho, pad, da.prep, da.pb, nullptr);
-    if (rc == 0 && !sym) rc = vbhmm_ppk_prepare(&db.m, rho, pad, db.prep, db.pb, nullptr);
-    if (rc == 0)
-      rc = vbhmm_ppk_gram(&da.m, da.prep, sym ? &da.m : &db.m, sym ? da.prep : db.prep, T, mode,
-                          static_cast<double *>(dout), nullptr);
-    if (rc == 0) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess && rc == 0 && out_bytes) e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
-  release(da);
-  release(db);
-  (void)hipFree(dout);
-  return rc != 0 ? rc : (int)e;
+  checklib::Pool pool;
+  const DevSet da = upload(sa, d, covmode, pool), db = sym ? da : upload(sb, d, covmode, pool);
+  double *dout = static_cast<double *>(pool.put(nullptr, out_bytes));
+  if (pool.e != hipSuccess) return (int)pool.e;
+  int rc = vbhmm_ppk_prepare(&da.m, rho, pad, da.prep, da.pb, nullptr);
+  if (rc == 0 && !sym) rc = vbhmm_ppk_prepare(&db.m, rho, pad, db.prep, db.pb, nullptr);
+  if (rc == 0) rc = vbhmm_ppk_gram(&da.m, da.prep, &db.m, db.prep, T, mode, dout, nullptr);
+  if (rc != 0) return rc;
+  pool.e = hipDeviceSynchronize();
+  pool.get(out, dout, out_bytes);
+  return (int)pool.e;
 }
 
 }  // extern "C"

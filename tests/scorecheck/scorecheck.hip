@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "device_pool.h"
+#include "host_prepare.h"
 #include "vbhmm_score.h"
 #include "vbhmm_score_pair.h"
 
@@ -52,20 +54,12 @@ long long scorecheck_host(int H, int KM, int d, int covmode, const int *nstates,
                           const double *trans, const double *mean, const double *cov, int N,
                           const int *offsets, const double *x, double *ll, double *vll, int *path) {
   const Layout L = make_layout(KM, d);
-  const bool diag = covmode == VBHEM_COV_DIAG;
-  const size_t cs = diag ? (size_t)d : (size_t)d * d;
-  std::vector<double> blocks((size_t)H * L.stride, 0.0);
-  long long bad = 0;
-  for (int h = 0; h < H; ++h)
-    for (int k = 0; k < KM; ++k)
-      if (!prepare_state(L, blocks.data() + (size_t)h * L.stride, k, nstates[h], d, diag,
-                         prior + (size_t)h * KM, trans + (size_t)h * KM * KM,
-                         mean + (size_t)h * KM * d, cov + (size_t)h * KM * cs) &&
-          !bad)
-        bad = 1 + (long long)h * KM + k;
+  std::vector<double> blocks;
+  const long long bad = checklib::host_prepare(L, H, KM, d, covmode, nstates, prior, trans, mean, cov, blocks);
   if (bad) return bad;
   const long long total = N > 0 ? offsets[N] : 0;
-  return dispatch(KM, d, HostPairs{L, blocks, H, N, d, diag, offsets, x, total, ll, vll, path});
+  return dispatch(KM, d,
+                  HostPairs{L, blocks, H, N, d, covmode == VBHEM_COV_DIAG, offsets, x, total, ll, vll, path});
 }
 
 // The same through vbhmm_score_prepare / _ll / _viterbi on device 0.  Returns the
@@ -73,50 +67,32 @@ long long scorecheck_host(int H, int KM, int d, int covmode, const int *nstates,
 int scorecheck_device(int H, int KM, int d, int covmode, const int *nstates, const double *prior,
                       const double *trans, const double *mean, const double *cov, int N,
                       const int *offsets, const double *x, double *ll, double *vll, int *path) {
-  const bool diag = covmode == VBHEM_COV_DIAG;
-  const size_t cs = diag ? (size_t)d : (size_t)d * d;
+  const size_t cs = covmode == VBHEM_COV_DIAG ? (size_t)d : (size_t)d * d;
   const long long total = N > 0 ? offsets[N] : 0;
-  vbhmm_score_hmms_t m = {H, KM, d, covmode, nullptr, nullptr, nullptr, nullptr, nullptr};
-  vbhmm_seqs_t s = {N, d, 0, nullptr, nullptr};
+  checklib::Pool pool;
+  vbhmm_score_hmms_t m = {H, KM, d, covmode,
+                          static_cast<const int *>(pool.put(nstates, (size_t)H * sizeof(int))),
+                          static_cast<const double *>(pool.put(prior, (size_t)H * KM * 8)),
+                          static_cast<const double *>(pool.put(trans, (size_t)H * KM * KM * 8)),
+                          static_cast<const double *>(pool.put(mean, (size_t)H * KM * d * 8)),
+                          static_cast<const double *>(pool.put(cov, (size_t)H * KM * cs * 8))};
+  vbhmm_seqs_t s = {N, d, 0, static_cast<const int *>(pool.put(offsets, (size_t)(N + 1) * sizeof(int))),
+                    static_cast<const double *>(pool.put(x, (size_t)total * d * 8))};
   const size_t pb = vbhmm_score_prepared_bytes(&m), wb = vbhmm_score_workspace_bytes(&m, total);
-  const size_t in_bytes[] = {(size_t)H * sizeof(int), (size_t)H * KM * 8, (size_t)H * KM * KM * 8,
-                             (size_t)H * KM * d * 8, (size_t)H * KM * cs * 8,
-                             (size_t)(N + 1) * sizeof(int), (size_t)total * d * 8};
-  const void *in_host[] = {nstates, prior, trans, mean, cov, offsets, x};
-  const size_t out_bytes[] = {(size_t)H * N * 8, (size_t)H * N * 8, (size_t)H * total * sizeof(int)};
-  void *out_host[] = {ll, vll, path};
-  void *din[7] = {nullptr}, *dout[3] = {nullptr}, *prep = nullptr, *ws = nullptr;
-  hipError_t e = hipSuccess;
-  int rc = 0;
-  for (int q = 0; q < 7 && e == hipSuccess; ++q) {
-    e = hipMalloc(&din[q], in_bytes[q] + 8);
-    if (e == hipSuccess && in_bytes[q]) e = hipMemcpy(din[q], in_host[q], in_bytes[q], hipMemcpyHostToDevice);
-  }
-  for (int q = 0; q < 3 && e == hipSuccess; ++q) e = hipMalloc(&dout[q], out_bytes[q] + 8);
-  if (e == hipSuccess) e = hipMalloc(&prep, pb + 8);
-  if (e == hipSuccess) e = hipMalloc(&ws, wb + 8);
-  if (e == hipSuccess) {
-    m.nstates = static_cast<const int *>(din[0]);
-    m.prior = static_cast<const double *>(din[1]);
-    m.trans = static_cast<const double *>(din[2]);
-    m.mean = static_cast<const double *>(din[3]);
-    m.cov = static_cast<const double *>(din[4]);
-    s.offsets = static_cast<const int *>(din[5]);
-    s.x = static_cast<const double *>(din[6]);
-    rc = vbhmm_score_prepare(&m, prep, pb, nullptr);
-    if (rc == 0) rc = vbhmm_score_ll(&m, prep, &s, static_cast<double *>(dout[0]), nullptr);
-    if (rc == 0)
-      rc = vbhmm_score_viterbi(&m, prep, &s, total, static_cast<int *>(dout[2]),
-                               static_cast<double *>(dout[1]), ws, wb, nullptr);
-    if (rc == 0) e = hipDeviceSynchronize();
-  }
-  for (int q = 0; q < 3 && e == hipSuccess && rc == 0; ++q)
-    if (out_bytes[q]) e = hipMemcpy(out_host[q], dout[q], out_bytes[q], hipMemcpyDeviceToHost);
-  for (void *p : din) (void)hipFree(p);
-  for (void *p : dout) (void)hipFree(p);
-  (void)hipFree(prep);
-  (void)hipFree(ws);
-  return rc != 0 ? rc : (int)e;
+  void *prep = pool.put(nullptr, pb), *ws = pool.put(nullptr, wb);
+  double *dll = static_cast<double *>(pool.put(nullptr, (size_t)H * N * 8));
+  double *dvll = static_cast<double *>(pool.put(nullptr, (size_t)H * N * 8));
+  int *dpath = static_cast<int *>(pool.put(nullptr, (size_t)H * total * sizeof(int)));
+  if (pool.e != hipSuccess) return (int)pool.e;
+  int rc = vbhmm_score_prepare(&m, prep, pb, nullptr);
+  if (rc == 0) rc = vbhmm_score_ll(&m, prep, &s, dll, nullptr);
+  if (rc == 0) rc = vbhmm_score_viterbi(&m, prep, &s, total, dpath, dvll, ws, wb, nullptr);
+  if (rc != 0) return rc;
+  pool.e = hipDeviceSynchronize();
+  pool.get(ll, dll, (size_t)H * N * 8);
+  pool.get(vll, dvll, (size_t)H * N * 8);
+  pool.get(path, dpath, (size_t)H * total * sizeof(int));
+  return (int)pool.e;
 }
 
 }  // extern "C"

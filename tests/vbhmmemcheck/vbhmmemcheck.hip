@@ -9,6 +9,7 @@
 #include <cmath>
 #include <vector>
 
+#include "device_pool.h"
 #include "vbhmm_em.h"
 #include "vbhmm_em_run.h"
 
@@ -16,23 +17,7 @@ namespace {
 
 using namespace vbhem::emrun;
 
-struct Pool {
-  std::vector<void *> p;
-  hipError_t e = hipSuccess;
-  void *put(const void *host, size_t bytes) {
-    void *q = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&q, bytes + 16);
-    if (e == hipSuccess && bytes && host) e = hipMemcpy(q, host, bytes, hipMemcpyHostToDevice);
-    p.push_back(q);
-    return q;
-  }
-  void get(void *host, const void *dev, size_t bytes) {
-    if (e == hipSuccess && bytes && host) e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-  }
-  ~Pool() {
-    for (void *q : p) (void)hipFree(q);
-  }
-};
+using checklib::Pool;
 
 void subject_maxima(int S, const int *offsets, const int *seq_first, int *max_seqs, int *max_obs) {
   *max_seqs = *max_obs = 0;
