@@ -76,6 +76,14 @@ class EmBatchOptT(ctypes.Structure):  # include/vbhmm_em.h vbhmm_em_opt_t
     _fields_ = [("max_iter", _c_int), ("min_diff", ctypes.c_double), ("chunk_runs", _c_int)]
 
 
+class GmmFitsT(ctypes.Structure):  # include/vbhmm_gmm.h vbhmm_gmm_fits_t
+    _fields_ = [("R", _c_int), ("KM", _c_int), ("subject", _vp), ("K", _vp), ("rows", _vp), ("reg", _vp)]
+
+
+class GmmOptT(ctypes.Structure):  # include/vbhmm_gmm.h vbhmm_gmm_opt_t
+    _fields_ = [("max_iter", _c_int), ("tolfun", ctypes.c_double), ("chunk_runs", _c_int)]
+
+
 class ScoreHmmsT(ctypes.Structure):  # include/vbhmm_score.h vbhmm_score_hmms_t
     _fields_ = [("H", _c_int), ("KM", _c_int), ("dim", _c_int), ("covmode", _c_int),
                 ("nstates", _vp), ("prior", _vp), ("trans", _vp), ("mean", _vp), ("cov", _vp)]
@@ -215,6 +223,10 @@ EXPORTS = {
                                 _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "vbhmm_em_gamma": (_c_int, [ctypes.POINTER(EmSubjectsT), ctypes.POINTER(EmRunsT), _vp, _vp, _vp,
                                 _c_int, _vp, _c_size, _vp]),
+    "vbhmm_gmm_fit_workspace_bytes": (_c_size, [ctypes.POINTER(EmSubjectsT), _c_int, _c_int, _c_int]),
+    "vbhmm_gmm_fit_batch": (_c_int, [ctypes.POINTER(EmSubjectsT), ctypes.POINTER(GmmFitsT),
+                                     ctypes.POINTER(GmmOptT), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.POINTER(EmHyperT), _vp, _vp, _c_size, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),

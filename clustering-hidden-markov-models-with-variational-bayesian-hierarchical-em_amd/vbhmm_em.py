@@ -85,12 +85,12 @@ def vbhmm_clip_hyps(opt: dict):
 # initialisation
 # ----------------------------------------------------------------------------
 def gmm_fit_randsample(X: np.ndarray, K: int, rng: np.random.Generator, tolfun: float = 1e-5,
-                       max_iter: int = 100, reg: float = 0.0) -> dict:
+                       max_iter: int = 100, reg: float = 0.0, trace: Optional[list] = None) -> dict:
     """Stand-in for MATLAB gmdistribution.fit(X, K, 'Start', 'randSample',
     'Options', struct('TolFun', 1e-5)) (vbhmm_init.m:59-60): K random rows of X
     as means, uniform proportions, every covariance diag(var(X)); full-covariance
     EM until |dLL| <= TolFun * |LL|.  Returns dict(prior [K], mean [K][dim],
-    cov [K][dim][dim])."""
+    cov [K][dim][dim]).  ``trace`` (a list) receives every iteration's log-likelihood."""
     N, dim = X.shape
     mu = X[rng.choice(N, K, replace=False)].copy()
     var = X.var(axis=0, ddof=1) if N > 1 else np.ones(dim)
@@ -107,6 +107,8 @@ def gmm_fit_randsample(X: np.ndarray, K: int, rng: np.random.Generator, tolfun: 
         mx = logp.max(1, keepdims=True)
         lse = mx[:, 0] + np.log(np.exp(logp - mx).sum(1))
         ll = lse.sum()
+        if trace is not None:
+            trace.append(float(ll))
         post = np.exp(logp - lse[:, None])
         nk = post.sum(0) + 1e-300
         pi = nk / N
@@ -465,14 +467,193 @@ def _initial_posterior(subjects, s: int, K: int, opt: dict, init: dict) -> dict:
     return vbhmm_init([subjects.X[s]], K, o, init)
 
 
-def _em_runs_desc(subjects, sub: np.ndarray, Ks: np.ndarray, post: np.ndarray, KM: int):
+def _check_init(init: str) -> bool:
+    if init not in ("host", "device"):
+        raise ValueError("init is 'host' or 'device'")
+    return init == "device"
+
+
+def _w0inv(opt: dict, dim: int):
+    """(W0^-1, W0mode) as :func:`vbhmm_init` takes them from the options."""
+    W0 = np.asarray(opt["W0"], dtype=np.float64)
+    W0m = float(W0) * np.eye(dim) if W0.size == 1 else np.diag(W0.reshape(-1))
+    return np.linalg.inv(W0m), ("iid" if W0.size == 1 else "diag")
+
+
+def _em_runs_desc(subjects, sub: np.ndarray, Ks: np.ndarray, post, KM: int):
+    """``post``: the packed posteriors [R][PL], a host array or a tensor already on the
+    subjects' device."""
     import torch
     from . import _capi
     dev = subjects.device
+    if not isinstance(post, torch.Tensor):
+        post = torch.from_numpy(np.ascontiguousarray(post, dtype=np.float64)).to(dev)
     t = dict(sub=torch.from_numpy(np.ascontiguousarray(sub, dtype=np.int32)).to(dev),
              K=torch.from_numpy(np.ascontiguousarray(Ks, dtype=np.int32)).to(dev),
-             post=torch.from_numpy(np.ascontiguousarray(post, dtype=np.float64)).to(dev))
+             post=post)
     return _capi.EmRunsT(len(sub), KM, _capi.ptr(t["sub"]), _capi.ptr(t["K"]), _capi.ptr(t["post"])), t
+
+
+# ----------------------------------------------------------------------------
+# batched GMM fits: the random trials' starting GMMs in one fused call
+# (include/vbhmm_gmm.h)
+# ----------------------------------------------------------------------------
+GMM_STATUS = ("converged", "max_iter", "ill_conditioned", "bad_fit")
+
+
+def _hyper_struct(hv: np.ndarray):
+    import ctypes
+    from . import _capi
+    return _capi.EmHyperT(hv[0], hv[1], hv[2], hv[3], (ctypes.c_double * 8)(*hv[4:12]),
+                          (ctypes.c_double * 8)(*hv[12:20]))
+
+
+def gmm_fit_batch(subjects, fits, tolfun: float = 1e-5, max_iter: int = 100, keep_lls: bool = False,
+                  hyper: Optional[np.ndarray] = None, chunk_runs: int = 0, KM: Optional[int] = None):
+    """:func:`gmm_fit_randsample` for every fit of ``fits`` in one fused call on the GPU
+    (vbhmm_gmm_fit_batch, include/vbhmm_gmm.h).  ``subjects`` is a
+    :class:`vbhmm.SubjectBatch`; ``fits`` a list of (subject index, K, rows, reg): the K
+    start rows index the subject's observations (what ``rng.choice(N, K, replace=False)``
+    gave).  One dict per fit: prior [K], mean [K][dim], cov [K][dim][dim] (None unless the
+    status is 'converged' or 'max_iter'), ll, iters, status (one of GMM_STATUS;
+    'ill_conditioned' is where numpy raises LinAlgError), ``lls`` with keep_lls.  With
+    ``hyper`` (:func:`em_hyper_vector` of clipped options) returns (results, post): the
+    device tensor [R][PL] of the packed initial posteriors of the fitted GMMs
+    (:func:`vbhmm_init`), rows of failed fits unwritten.  2 <= K <= 8 and dim <= 8; ``KM``
+    (4 or 8) fixes the padding of ``post``, by default the bucket of the largest K."""
+    import ctypes
+    import torch
+    from . import _capi
+    if not len(fits):
+        return ([], None) if hyper is not None else []
+    lib = _capi.lib()
+    dim, dev = subjects.dim, subjects.device
+    R = len(fits)
+    Ks = np.array([int(f[1]) for f in fits], dtype=np.int32)
+    if KM is None:
+        KM = 4 if Ks.max() <= 4 else 8 if Ks.max() <= FUSED_MAX_K else 16
+    rows = np.zeros((R, KM), dtype=np.int32)
+    for i, f in enumerate(fits):
+        r = np.asarray(f[2], dtype=np.int64).reshape(-1)
+        if r.size != Ks[i]:
+            raise ValueError("a fit needs K start rows")
+        rows[i, :min(r.size, KM)] = r[:KM]
+    f64 = torch.float64
+    d_sub = torch.from_numpy(np.array([int(f[0]) for f in fits], dtype=np.int32)).to(dev)
+    d_K, d_rows = torch.from_numpy(Ks).to(dev), torch.from_numpy(rows).to(dev)
+    d_reg = torch.from_numpy(np.array([float(f[3]) for f in fits], dtype=np.float64)).to(dev)
+    ft = _capi.GmmFitsT(R, KM, _capi.ptr(d_sub), _capi.ptr(d_K), _capi.ptr(d_rows), _capi.ptr(d_reg))
+    go = _capi.GmmOptT(int(max_iter), float(tolfun), int(chunk_runs))
+    o_pr = torch.zeros((R, KM), dtype=f64, device=dev)
+    o_me = torch.zeros((R, KM, dim), dtype=f64, device=dev)
+    o_co = torch.zeros((R, KM, dim, dim), dtype=f64, device=dev)
+    o_ll = torch.zeros(R, dtype=f64, device=dev)
+    o_it, o_st = (torch.zeros(R, dtype=torch.int32, device=dev) for _ in range(2))
+    o_lls = torch.zeros((R, int(max_iter)), dtype=f64, device=dev) if keep_lls else None
+    o_post = torch.zeros((R, em_post_len(KM, dim)), dtype=f64, device=dev) if hyper is not None else None
+    hy = _hyper_struct(np.asarray(hyper, dtype=np.float64)) if hyper is not None else None
+    sd = subjects.desc()
+    nb = int(lib.vbhmm_gmm_fit_workspace_bytes(ctypes.byref(sd), R, KM, int(chunk_runs)))
+    ws = _capi.workspace(nb, dev)
+    _capi.check(lib.vbhmm_gmm_fit_batch(ctypes.byref(sd), ctypes.byref(ft), ctypes.byref(go), _capi.ptr(o_pr),
+                                        _capi.ptr(o_me), _capi.ptr(o_co), _capi.ptr(o_ll), _capi.ptr(o_it),
+                                        _capi.ptr(o_st), _capi.ptr(o_lls),
+                                        ctypes.byref(hy) if hy is not None else None, _capi.ptr(o_post),
+                                        _capi.ptr(ws), ws.numel(), _capi.stream(dev)), "vbhmm_gmm_fit_batch")
+    h_pr, h_me, h_co = o_pr.cpu().numpy(), o_me.cpu().numpy(), o_co.cpu().numpy()
+    h_ll, h_it, h_st = o_ll.cpu().numpy(), o_it.cpu().numpy(), o_st.cpu().numpy()
+    h_lls = o_lls.cpu().numpy() if keep_lls else None
+    out = []
+    for r in range(R):
+        K, done = int(Ks[r]), int(h_st[r]) < 2
+        g = dict(prior=h_pr[r, :K].copy() if done else None, mean=h_me[r, :K].copy() if done else None,
+                 cov=h_co[r, :K].copy() if done else None, ll=float(h_ll[r]), iters=int(h_it[r]),
+                 status=GMM_STATUS[int(h_st[r])])
+        if keep_lls:
+            # a fit that fails at the factorisation of iteration iters has no ll of that iteration
+            g["lls"] = h_lls[r, :g["iters"] - (int(h_st[r]) == 2)].copy()
+        out.append(g)
+    return (out, o_post) if hyper is not None else out
+
+
+def random_gmm_batch(subjects, Ks, opt: dict, fit_batch=None, hyper: Optional[np.ndarray] = None,
+                     info: Optional[dict] = None, skip=()) -> dict:
+    """The GMMs of every (subject, K, trial) as :func:`_draw_inits` / :func:`random_gmm`
+    define them, generator stream included, with the fits of all of them in batched calls
+    (``fit_batch``: :func:`gmm_fit_batch` or a stand-in with its signature).  Returns
+    {(subject, K): [gmm of each trial]}; pairs in ``skip`` are left out.
+
+    K = 1 and N <= K are closed forms on the host and consume no draws.  For the rest each
+    (subject, K) has its own default_rng(opt['seed']) and the numtrials row sets are drawn
+    up front; one call fits them all.  Where a (subject, K) has an ill-conditioned trial,
+    t its first, the host path draws once more and refits trial t with reg = 1e-10, then
+    goes on: so the generator is replayed through trial t, the regularised start of t and
+    new starts of the trials after t are drawn, and those fits go into the next call, until
+    a round brings no new failure (at most numtrials rounds, one call each).  A regularised
+    fit that fails again raises numpy.linalg.LinAlgError, as the host path does.
+
+    ``info`` (a dict) receives rounds, regularised {(subject, K): [trials]}, draws
+    {(subject, K): count} and, with ``hyper``, post_rounds (each call's device tensor of
+    packed initial posteriors) and post_src {(subject, K): [(round, row) of each trial]}."""
+    from . import _capi
+    fit = fit_batch if fit_batch is not None else gmm_fit_batch
+    Ks = [int(k) for k in np.atleast_1d(Ks)]
+    KM = 4 if max(Ks) <= 4 else 8
+    numtrials = int(opt["numtrials"])
+    out, plan, src = {}, {}, {}
+    for s, X in enumerate(subjects.X):
+        N = X.shape[0]
+        for K in Ks:
+            if (s, K) in skip:
+                continue
+            if K == 1 or N <= K:
+                rng = np.random.default_rng(opt["seed"])
+                out[(s, K)] = [random_gmm([X], K, rng) for _ in range(1 if K == 1 else numtrials)]
+                continue
+            rng = np.random.default_rng(opt["seed"])
+            plan[(s, K)] = dict(rows=[rng.choice(N, K, replace=False) for _ in range(numtrials)],
+                                reg=[0.0] * numtrials, regd=[])
+            out[(s, K)] = [None] * numtrials
+            src[(s, K)] = [None] * numtrials
+    todo = [(key, t) for key in plan for t in range(numtrials)]
+    rounds, posts = 0, []
+    while todo:
+        fits = [(key[0], key[1], plan[key]["rows"][t], plan[key]["reg"][t]) for key, t in todo]
+        res = fit(subjects, fits, hyper=hyper, KM=KM)
+        if hyper is not None:
+            res, post = res
+            posts.append(post)
+        first_fail = {}
+        for i, ((key, t), g) in enumerate(zip(todo, res)):
+            if g["status"] == "bad_fit":
+                raise _capi.VbhemError("gmm_fit_batch: a fit's subject, K or rows are out of range")
+            if g["status"] == "ill_conditioned":
+                if plan[key]["reg"][t] > 0:
+                    raise np.linalg.LinAlgError("the regularised GMM fit is ill-conditioned too")
+                first_fail.setdefault(key, t)    # todo is in trial order: the first failure
+            elif key not in first_fail:
+                out[key][t] = dict(prior=g["prior"], mean=g["mean"], cov=g["cov"])
+                src[key][t] = (rounds, i)
+        rounds += 1
+        todo = []
+        for key, t in first_fail.items():
+            p, N = plan[key], subjects.X[key[0]].shape[0]
+            p["regd"].append(t)
+            rng = np.random.default_rng(opt["seed"])
+            for u in range(numtrials):
+                r = rng.choice(N, key[1], replace=False)
+                if u in p["regd"]:               # the failed draw, then the regularised fit's own
+                    r = rng.choice(N, key[1], replace=False)
+                if u >= t:
+                    p["rows"][u] = r
+            p["reg"][t] = 1e-10
+            todo += [(key, u) for u in range(t, numtrials)]
+    if info is not None:
+        info.update(rounds=rounds, regularised={k: list(p["regd"]) for k, p in plan.items() if p["regd"]},
+                    draws={k: numtrials + len(p["regd"]) for k, p in plan.items()})
+        if hyper is not None:
+            info.update(post_rounds=posts, post_src=src)
+    return out
 
 
 def vbhmm_em_gamma(subjects, items, chunk_runs: int = 0) -> list:
@@ -537,7 +718,8 @@ def fill_gamma(subjects, hmms: Sequence[dict], chunk_runs: int = 0) -> None:
 
 
 def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = False, gamma: bool = False,
-                   finish: bool = True, chunk_runs: int = 0, timing: Optional[dict] = None) -> list:
+                   finish: bool = True, chunk_runs: int = 0, timing: Optional[dict] = None,
+                   post=None) -> list:
     """The EM of :func:`vbhmm_em` for every run of ``runs`` in one fused call on the GPU
     (vbhmm_em_batch, include/vbhmm_em.h): no host round trip inside the loop.
 
@@ -548,7 +730,10 @@ def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = Fals
     ``dLL`` with opt['calc_LLderiv'], ``pdf`` unless finish=False: see
     :func:`em_output_pdf`), plus ``subject``, ``status`` and ``varpar_estep``, the
     posterior at the last E-step (``gamma``, ``dLL``, ``N1``, ``N``, ``M`` belong to it).
-    K <= 8 and dim <= 8; no fix_clusters / fix_cov.  ``timing`` (a dict) receives the
+    K <= 8 and dim <= 8; no fix_clusters / fix_cov.  ``post``: a device tensor [R][PL] of
+    packed initial posteriors (:func:`pack_posterior`, padded to the bucket of the largest
+    K) used as they are, with runs given as (subject index, K, None): no host
+    initialisation.  ``timing`` (a dict) receives the
     seconds of the call's three parts: init (vbhmm_init + packing, host), device (the
     fused call up to the copy back), unpack (host)."""
     import ctypes
@@ -569,10 +754,16 @@ def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = Fals
     sub = np.array([int(r[0]) for r in runs])
     Ks = np.array([int(r[1]) for r in runs])
     KM = 4 if Ks.max() <= 4 else 8 if Ks.max() <= FUSED_MAX_K else 16
-    mixes = [_initial_posterior(subjects, s, K, opt, r[2]) for s, K, r in zip(sub, Ks, runs)]
-    W0inv, W0mode = mixes[0]["W0inv"], mixes[0]["W0mode"]
     PL, SL = em_post_len(KM, dim), em_stats_len(KM, dim)
-    post = np.stack([pack_posterior(mx, K, KM, dim) for mx, K in zip(mixes, Ks)])
+    if post is None:
+        mixes = [_initial_posterior(subjects, s, K, opt, r[2]) for s, K, r in zip(sub, Ks, runs)]
+        W0inv, W0mode = mixes[0]["W0inv"], mixes[0]["W0mode"]
+        post = np.stack([pack_posterior(mx, K, KM, dim) for mx, K in zip(mixes, Ks)])
+    else:
+        if (tuple(post.shape) != (len(runs), PL) or post.dtype != torch.float64 or post.device != subjects.device
+                or not post.is_contiguous()):
+            raise ValueError(f"post is a contiguous float64 tensor [{len(runs)}][{PL}] where the subjects live")
+        W0inv, W0mode = _w0inv(opt, dim)
     rn, keep = _em_runs_desc(subjects, sub, Ks, post, KM)
     hv = em_hyper_vector(opt, W0inv)
     hy = _capi.EmHyperT(hv[0], hv[1], hv[2], hv[3], (ctypes.c_double * 8)(*hv[4:12]),
@@ -733,19 +924,22 @@ def vbhmm_em_hyp(data: Sequence[np.ndarray], K: int, opt: dict, inithmm: dict, d
 
 
 def vbhmm_learn(data: Sequence[np.ndarray], Ks, opt: dict, device="cuda",
-                gmms: Optional[dict] = None, engine: str = "loop") -> dict:
+                gmms: Optional[dict] = None, engine: str = "loop", init: str = "host") -> dict:
     """vbhmm_learn.m (initmode 'random'): for each K, numtrials EM runs from random
     GMMs (seeded by opt['seed'], vbhmm_learn.m:443-451; K = 1 needs one); with
     opt['learn_hyps'] every unique trial (uniqueLL, 2 minDiff 10 apart) is re-run
     through :func:`vbhmm_em_hyp` (:482-552); keep the best bound; over several K,
     select by LL + gammaln(K+1) (:367-405).  ``gmms[K]`` = list of GMMs to inject
     instead of random draws.  engine="fused": the EM runs of every K and trial in one
-    :func:`vbhmm_em_batch` call (the loop engine where that does not apply)."""
+    :func:`vbhmm_em_batch` call (the loop engine where that does not apply).
+    init="device": under the fused engine the random trials' GMMs are fitted on the GPU
+    too (:func:`random_gmm_batch`; "host" wherever the fused engine does not apply)."""
     Ks = [int(k) for k in np.atleast_1d(Ks)]
     dim = len(opt["mu0"])
     data = [np.asarray(a, dtype=np.float64).reshape(-1, dim) for a in data]
+    _check_init(init)
     if _check_engine(engine) and fused_supported(opt, Ks, dim):
-        return _learn_fused([data], Ks, opt, device, [gmms])[0]
+        return _learn_fused([data], Ks, opt, device, [gmms], init=init)[0]
     sb = vbhmm.SequenceBatch(data, dim, device)
     out_all = []
     for K in Ks:
@@ -755,24 +949,81 @@ def vbhmm_learn(data: Sequence[np.ndarray], Ks, opt: dict, device="cuda",
     return _learn_select(out_all, Ks, opt)
 
 
-def _learn_fused(datas, Ks: list, opt: dict, device, gmms_list, subjects=None) -> list:
+def _device_inits(sbt, Ks: list, opt: dict, gmms_list, runs: list, where: list, timing: Optional[dict]):
+    """init="device" of :func:`_learn_fused`: fills ``runs`` with (subject, K, None) and
+    ``where`` in the order of the host path and returns the device tensor [R][PL] of their
+    packed initial posteriors.  The fitted GMMs' rows come from :func:`random_gmm_batch`
+    and never leave the device; the rows of injected GMMs and of the host's closed forms
+    (K = 1, N <= K) are packed on the host and copied into their places."""
+    import time
+    import torch
+    t0 = time.perf_counter()
+    dim, dev = sbt.dim, sbt.device
+    copt, _ = vbhmm_clip_hyps(opt)
+    KM = 4 if max(Ks) <= 4 else 8
+    given = {(s, K): list(g[K]) for s, g in enumerate(gmms_list or []) if g is not None for K in Ks if K in g}
+    info = {}
+    drawn = random_gmm_batch(sbt, Ks, opt, hyper=em_hyper_vector(copt, _w0inv(copt, dim)[0]), info=info,
+                             skip=given)
+    t1 = time.perf_counter()
+    base = np.concatenate([[0], np.cumsum([p.shape[0] for p in info["post_rounds"]])]).astype(np.int64)
+    dev_rows, dev_src, host_rows, host_post = [], [], [], []
+    for s in range(sbt.S):
+        for K in Ks:
+            gm = given.get((s, K), drawn.get((s, K)))
+            src = info["post_src"].get((s, K)) if (s, K) not in given else None
+            for t, g in enumerate(gm):
+                if src is not None:
+                    dev_rows.append(len(runs))
+                    dev_src.append(base[src[t][0]] + src[t][1])
+                else:
+                    host_rows.append(len(runs))
+                    host_post.append(pack_posterior(_initial_posterior(sbt, s, K, copt, g), K, KM, dim))
+                runs.append((s, K, None))
+                where.append((s, K))
+    post = torch.empty((len(runs), em_post_len(KM, dim)), dtype=torch.float64, device=dev)
+    if dev_rows:
+        allp = torch.cat(info["post_rounds"])
+        post[torch.from_numpy(np.array(dev_rows, dtype=np.int64)).to(dev)] = \
+            allp[torch.from_numpy(np.array(dev_src, dtype=np.int64)).to(dev)]
+    if host_rows:
+        post[torch.from_numpy(np.array(host_rows, dtype=np.int64)).to(dev)] = \
+            torch.from_numpy(np.stack(host_post)).to(dev)
+    if timing is not None:
+        timing["gmm"] = timing.get("gmm", 0.0) + (t1 - t0)
+        timing["gmm_rounds"] = timing.get("gmm_rounds", 0) + info["rounds"]
+        timing["init"] = timing.get("init", 0.0) + (time.perf_counter() - t1)
+    return post
+
+
+def _learn_fused(datas, Ks: list, opt: dict, device, gmms_list, subjects=None, init: str = "host",
+                 timing: Optional[dict] = None) -> list:
     """vbhmm_learn for every subject under the fused engine: the GMMs of all subjects, Ks
     and trials are drawn on the host exactly as the loop engine draws them, ONE
     :func:`vbhmm_em_batch` call runs them all (ordered by subject, so neighbouring
     wavefronts read the same data), then each subject's trials go through the same
     selection.  Output Gaussians are computed for every run (they are cheap next to the
     GMM fits); gamma comes from one more fused call for each (subject, K)'s best random
-    trial."""
+    trial.  init="device": the GMMs are fitted on the GPU (:func:`random_gmm_batch`, the
+    same draws) and their packed initial posteriors go straight into the EM call; injected
+    ``gmms`` win.  ``timing`` (a dict) receives the seconds of the parts."""
     dim = len(opt["mu0"])
     sbt = subjects if subjects is not None else vbhmm.SubjectBatch(datas, dim, device)
     runs, where = [], []
-    for s, data in enumerate(sbt.datas):
-        g = gmms_list[s] if gmms_list is not None else None
-        for K in Ks:
-            for init in _draw_inits(data, K, opt, g):
-                runs.append((s, K, init))
-                where.append((s, K))
-    res = vbhmm_em_batch(sbt, runs, opt, keep_LLs=True)
+    if _check_init(init):
+        post = _device_inits(sbt, Ks, opt, gmms_list, runs, where, timing)
+    else:
+        import time
+        post, t0 = None, time.perf_counter()
+        for s, data in enumerate(sbt.datas):
+            g = gmms_list[s] if gmms_list is not None else None
+            for K in Ks:
+                for gmm in _draw_inits(data, K, opt, g):
+                    runs.append((s, K, gmm))
+                    where.append((s, K))
+        if timing is not None:
+            timing["gmm"] = timing.get("gmm", 0.0) + (time.perf_counter() - t0)
+    res = vbhmm_em_batch(sbt, runs, opt, keep_LLs=True, timing=timing, post=post)
     per = {}
     for w, h in zip(where, res):
         per.setdefault(w, []).append(h)
@@ -911,7 +1162,8 @@ def _do_learn_hyps(v) -> bool:
 
 
 def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, device="cuda",
-                      gmms: Optional[list] = None, engine: str = "loop"):
+                      gmms: Optional[list] = None, engine: str = "loop", init: str = "host",
+                      timing: Optional[dict] = None):
     """vbhmm_learn_batch.m: one vbhmm_learn per subject; returns (hmms, LLs).  With
     opt['learn_hyps_batch'] (:84-189) one set of hyperparameters shared by every
     subject: each subject's unique random trials (keep_suboptimal_hmms) seed EM runs,
@@ -922,19 +1174,25 @@ def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, devi
     engine="fused": the EM runs of all subjects, Ks and trials are one
     :func:`vbhmm_em_batch` call, and every evaluation of the shared-hyperparameter
     objective is one call over all (subject, suboptimal HMM) runs; fix_clusters,
-    fix_cov, K > 8 and dim > 8 stay with the loop engine."""
+    fix_cov, K > 8 and dim > 8 stay with the loop engine.
+
+    init="device": under the fused engine the GMMs of all random trials are fitted in
+    batched GPU calls (:func:`random_gmm_batch`, the draws of the host path) and their
+    initial posteriors never leave the device; "host" wherever the fused engine does not
+    apply.  ``timing`` (a dict) receives the seconds of the fused engine's parts."""
     lhb = opt.get("learn_hyps_batch", 0)
     Ks = [int(k) for k in np.atleast_1d(Ks)]
     fused = _check_engine(engine) and fused_supported(opt, Ks, len(opt["mu0"]))
+    _check_init(init)
     if not (isinstance(lhb, (list, tuple)) or lhb):
         if fused:
-            hmms = _learn_fused(datas, Ks, opt, device, gmms)
+            hmms = _learn_fused(datas, Ks, opt, device, gmms, init=init, timing=timing)
             return hmms, np.array([h["LL"] for h in hmms])
         hmms = [vbhmm_learn(d, Ks, opt, device, gmms[i] if gmms is not None else None)
                 for i, d in enumerate(datas)]
         return hmms, np.array([h["LL"] for h in hmms])
     from . import hyp
-    grad_batch, X0, info, opt = hyps_batch_objective(datas, Ks, opt, device, gmms, engine)
+    grad_batch, X0, info, opt = hyps_batch_objective(datas, Ks, opt, device, gmms, engine, init)
     methods = {"minimize-bfgs": "BFGS", "minimize-lbfgs": "LBFGS", "minimize-cg": "CG"}
     name = opt.get("minimizer", "minimize-bfgs")
     if name not in methods:
@@ -950,7 +1208,7 @@ def vbhmm_learn_batch(datas: Sequence[Sequence[np.ndarray]], Ks, opt: dict, devi
 
 
 def hyps_batch_objective(datas, Ks, opt: dict, device="cuda", gmms: Optional[list] = None,
-                         engine: str = "loop"):
+                         engine: str = "loop", init: str = "host"):
     """The objective of opt['learn_hyps_batch'] (vbhmm_grad_batch_parfor,
     vbhmm_learn_batch.m:347-457): learns every subject's unique random trials, then
     returns (grad_batch, X0, hypinfo, options) with grad_batch(X, keep=False) -> (mean
@@ -959,6 +1217,7 @@ def hyps_batch_objective(datas, Ks, opt: dict, device="cuda", gmms: Optional[lis
     lhb = opt["learn_hyps_batch"]
     Ks = [int(k) for k in np.atleast_1d(Ks)]
     fused = _check_engine(engine) and fused_supported(opt, Ks, len(opt["mu0"]))
+    _check_init(init)
     if not isinstance(lhb, (list, tuple)):
         if lhb != 1:
             raise ValueError("learn_hyps_batch not set properly")
@@ -970,7 +1229,7 @@ def hyps_batch_objective(datas, Ks, opt: dict, device="cuda", gmms: Optional[lis
     iopt = dict(opt, keep_suboptimal_hmms=1)
     if fused:
         sbt = vbhmm.SubjectBatch(datas, dim, device)
-        inithmms = _learn_fused(datas, Ks, iopt, device, gmms, subjects=sbt)
+        inithmms = _learn_fused(datas, Ks, iopt, device, gmms, subjects=sbt, init=init)
     else:
         batches = [vbhmm.SequenceBatch(d, dim, device) for d in datas]
         inithmms = [vbhmm_learn(d, Ks, iopt, device, gmms[i] if gmms is not None else None)

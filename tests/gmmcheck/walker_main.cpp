@@ -1,0 +1,108 @@
+// tests/gmmcheck/walker_main.cpp -- TEST-ONLY stand-alone program: the serial walker of
+// csrc/vbhmm_gmm_run.h on seeded inputs, for a run under the address and undefined-behaviour
+// sanitizers on the CPU (`make gmm_sanitize`; plain C++, no device compiler).  It walks
+// every shape class the kernel has: KM = 4 and 8, dim = 2, 3 and 8, N at the edges of a
+// round of lanes and N = K + 1, start rows 0 and N - 1, the initial posterior, a fit that
+// stops at max_iter, an ill-conditioned fit with its regularised refit, and bad fits.
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "vbhmm_gmm_run.h"
+
+using namespace vbhem::gmmrun;
+
+namespace {
+
+struct Lcg {
+  unsigned long long s;
+  double uni() {
+    s = s * 6364136223846793005ULL + 1442695040888963407ULL;
+    return (double)(s >> 11) / 9007199254740992.0;
+  }
+  double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
+};
+
+Hyper hyper_of(int dim) {
+  Hyper h;
+  h.alpha0 = h.epsilon0 = h.beta0 = 1.0;
+  h.v0 = dim + 8.0;
+  for (int a = 0; a < kMaxDim; ++a) {
+    h.m0[a] = 180.0;
+    h.W0inv[a] = 1000.0;
+  }
+  return h;
+}
+
+// mode 0: an ordinary fit; 1: max_iter = 2; 2: one far point among the start rows (ill-
+// conditioned), then the same rows with reg = 1e-10; 3: bad fits; 4: whatever status the
+// fit ends with (N = K + 1 collapses onto single points)
+template <int KM>
+int one_case(int K, int dim, int N, unsigned long long seed, int mode) {
+  Lcg g{seed};
+  std::vector<double> x((size_t)N * dim);
+  for (int n = 0; n < N; ++n) {
+    const int z = g.uni() < 0.5;
+    for (int a = 0; a < dim; ++a) x[(size_t)n * dim + a] = (z ? 150.0 : 210.0) + 10.0 * a + 20.0 * g.normal();
+  }
+  std::vector<int> rows(KM, 0);
+  for (int k = 0; k < K; ++k) rows[k] = k == 0 ? N - 1 : k == 1 ? 0 : (int)((long long)k * N / K);
+  if (mode == 2)
+    for (int a = 0; a < dim; ++a) x[(size_t)(N - 1) * dim + a] = 1e4;
+  const Hyper h = hyper_of(dim);
+  const int PL = vbhem::emrun::post_len(KM, dim), max_iter = mode == 1 ? 2 : 100;
+  std::vector<double> prior(KM, -1.0), mean(KM * dim, -1.0), cov(KM * dim * dim, -1.0), lls(max_iter, 0.0),
+      post(PL, -1.0), wp((size_t)N * KM), wl(N);
+  const Work w{wp.data(), wl.data()};
+  int bad = 0;
+  if (mode == 3) {
+    const int far[KM] = {0, N};
+    FitResult r = run_serial<KM>(1, dim, N, N, x.data(), rows.data(), 0.0, max_iter, 1e-5, prior.data(), mean.data(),
+                                 cov.data(), lls.data(), &h, post.data(), w);
+    bad += r.status != kBadFit;
+    r = run_serial<KM>(2, dim, 2, N, x.data(), rows.data(), 0.0, max_iter, 1e-5, prior.data(), mean.data(),
+                       cov.data(), lls.data(), &h, post.data(), w);
+    bad += r.status != kBadFit;
+    r = run_serial<KM>(2, dim, N, N, x.data(), far, 0.0, max_iter, 1e-5, prior.data(), mean.data(), cov.data(),
+                       lls.data(), &h, post.data(), w);
+    bad += r.status != kBadFit || prior[0] != -1.0 || post[0] != -1.0;
+    std::printf("KM=%d bad fits: %s\n", KM, bad ? "FAILED" : "refused");
+    return bad;
+  }
+  FitResult r = run_serial<KM>(K, dim, N, N, x.data(), rows.data(), 0.0, max_iter, 1e-5, prior.data(), mean.data(),
+                               cov.data(), lls.data(), &h, post.data(), w);
+  std::printf("KM=%d K=%d dim=%d N=%d mode=%d: ll=%.12g iters=%d status=%d\n", KM, K, dim, N, mode, r.ll, r.iters,
+              r.status);
+  if (mode == 1) return !(r.status == kMaxIter && r.iters == 2);
+  if (mode == 2) {
+    bad += !(r.status == kIllConditioned && prior[0] == -1.0 && post[0] == -1.0);
+    r = run_serial<KM>(K, dim, N, N, x.data(), rows.data(), 1e-10, max_iter, 1e-5, prior.data(), mean.data(),
+                       cov.data(), lls.data(), &h, post.data(), w);
+    std::printf("  reg=1e-10: ll=%.12g iters=%d status=%d\n", r.ll, r.iters, r.status);
+    return bad + !(r.status == kConverged && std::isfinite(r.ll));
+  }
+  if (mode == 4) return 0;
+  double sp = 0.0;
+  for (int k = 0; k < K; ++k) sp += prior[k];
+  return !(std::isfinite(r.ll) && r.status != kIllConditioned && std::fabs(sp - 1.0) < 1e-12 && post[0] > 1.0);
+}
+
+}  // namespace
+
+int main() {
+  int bad = 0;
+  bad += one_case<4>(2, 2, 250, 1, 0);
+  bad += one_case<4>(3, 2, 63, 2, 0);
+  bad += one_case<4>(4, 3, 64, 3, 0);
+  bad += one_case<4>(2, 2, 65, 4, 0);
+  bad += one_case<4>(2, 2, 129, 5, 0);
+  bad += one_case<4>(3, 2, 4, 6, 4);
+  bad += one_case<8>(8, 2, 300, 7, 0);
+  bad += one_case<8>(5, 8, 400, 8, 0);
+  bad += one_case<4>(2, 2, 250, 9, 1);
+  bad += one_case<4>(2, 2, 41, 10, 2);
+  bad += one_case<4>(2, 2, 40, 11, 3);
+  bad += one_case<8>(2, 2, 40, 12, 3);
+  std::printf(bad ? "FAILED %d\n" : "walker OK\n", bad);
+  return bad != 0;
+}
