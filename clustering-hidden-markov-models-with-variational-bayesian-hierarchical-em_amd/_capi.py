@@ -227,6 +227,11 @@ EXPORTS = {
     "vbhmm_gmm_fit_batch": (_c_int, [ctypes.POINTER(EmSubjectsT), ctypes.POINTER(GmmFitsT),
                                      ctypes.POINTER(GmmOptT), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(EmHyperT), _vp, _vp, _c_size, _vp]),
+    "vbhem_wtk_cluster_workspace_bytes": (_c_size, [_c_int] * 5),
+    "vbhem_wtk_cluster_batch": (_c_int, [_c_int] * 4 + [_vp] * 4 + [_c_int] + [_vp] * 5 + [_c_size, _vp]),
+    "vbhem_wtk_states_workspace_bytes": (_c_size, [ctypes.c_longlong]),
+    "vbhem_wtk_states_batch": (_c_int, [_c_int] * 5 + [_vp, _vp, _c_int] + [_vp] * 4 + [ctypes.c_longlong]
+                               + [_vp] * 6 + [_c_size, _vp]),
     "vbhem_last_error": (ctypes.c_char_p, []),
     "vbhem_last_kernel": (ctypes.c_char_p, [_c_int]),
     "vbhem_version": (ctypes.c_char_p, []),

@@ -17,7 +17,9 @@ Initialisation (opt['initmode']): 'baseem' (the default here; vbhemhmm_init.m:58
 with its draws from a numpy generator seeded by seed + trial (vbhem_h3m_c.m:32-38
 seeds MATLAB's twister the same way), 'wtkmeans' (vbhemhmm_init.m:294-425:
 weighted k-means of the base states' means, h3m.wtkmeans_init; MATLAB's kmeans
-replaced by a k-means++ stand-in), 'gmmNew' (vbhemhmm_init.m:103-293: the base
+replaced by a k-means++ stand-in; opt['init_engine'] = 'device' runs every trial's k-means
+in batched device calls, h3m.wtkmeans_init_batch, the default 'host' one trial after
+another in numpy), 'gmmNew' (vbhemhmm_init.m:103-293: the base
 Gaussians reduced by hierarchical EM, GMM_MixHierEM.m, h3m.gmmnew_init), or 'auto'
 (vbhem_h3m_cluster.m:359-395: each of the three, the best bound wins).
 """
@@ -32,7 +34,8 @@ from scipy.special import gammaln
 from . import em
 from .estep import EStepEngine
 from .h3m import (COV_FULL, BaseSet, baseem_draws, baseem_init, default_options, hmms_to_h3m_hem,
-                  hmms_to_h3m_hem_device, gmmnew_init, wtkmeans_init, wtkmeans_points)
+                  hmms_to_h3m_hem_device, gmmnew_init, wtkmeans_init, wtkmeans_init_batch,
+                  wtkmeans_points)
 
 
 def unique_ll(LLall: Sequence[float], diffthresh: float) -> List[int]:
@@ -77,13 +80,21 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     initmode = opt.get("initmode", "baseem")
     if initmode not in ("baseem", "wtkmeans", "gmmNew"):
         raise ValueError(f"initmode {initmode!r}: 'baseem', 'gmmNew' or 'wtkmeans'")
-    pts = wtkmeans_points(base, opt.get("initopt_mode", "r0")) if initmode == "wtkmeans" else None
+    init_engine = opt.get("init_engine", "host")
+    if init_engine not in ("host", "device"):
+        raise ValueError(f"init_engine {init_engine!r}: 'host' or 'device'")
+    # init_engine='device': the k-means of every 'wtkmeans' trial in batched device calls
+    # (h3m.wtkmeans_init_batch); the other modes have no device path and run on the host
+    batched = init_engine == "device" and initmode == "wtkmeans"
+    if batched:
+        posts = wtkmeans_init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
+    pts = wtkmeans_points(base, opt.get("initopt_mode", "r0")) if initmode == "wtkmeans" and not batched else None
     if initmode == "gmmNew":
         bn = base.numpy()
         ns = bn["nstates"]
         pts = (np.concatenate([bn["centres"][i, :int(ns[i])] for i in range(base.N)]),
                np.concatenate([bn["covars"][i, :int(ns[i])] for i in range(base.N)]))
-    for it in range(1, R + 1):
+    for it in range(1, R + 1) if not batched else ():
         if initmode == "wtkmeans":  # vbhem_h3m_c.m:52-54: wtseed = seed + trial
             posts.append(wtkmeans_init(base, opt, int(opt["seed"]) + it, pts))
         elif initmode == "gmmNew":  # (the trial's stream: rng(seed + trial), :32-38)

@@ -465,6 +465,14 @@ def wtkmeans_init(base: BaseSet, opt: dict, wtseed: int, points=None) -> Posteri
         else:
             g2 = np.random.Generator(np.random.PCG64(wtseed + 1))
             centres[i] = kmeans_pp(mi, S, g2)
+    return _wtk_posterior(opt, mode, Kb, d, base.covmode, centres, g2, c11)
+
+
+def _wtk_posterior(opt: dict, mode: str, Kb: int, d: int, covmode: int, centres: list, g2, c11) -> Posterior:
+    """The rest of 'wtkmeans' after the state centres (vbhemhmm_init.m:372-425): an empty
+    cluster takes the first non-empty cluster's centres, prior / A per cluster from ``g2``
+    (makeAprior), the counts and W.  ``opt`` is already clipped."""
+    K, S = opt["K"], opt["S"]
     first = next(i for i in range(K) if centres[i] is not None)
     centres = [c if c is not None else centres[first] for c in centres]
     Nv = opt["Nv"] * Kb
@@ -478,13 +486,199 @@ def wtkmeans_init(base: BaseSet, opt: dict, wtseed: int, points=None) -> Posteri
         eps[j] = A * NJ + opt["epsilon0"]
     v = np.full((K, S), opt["v0"] + nsj + 1)
     lam = np.full((K, S), opt["lambda0"] + nsj)
-    if base.covmode == COV_DIAG:
+    if covmode == COV_DIAG:
         W = np.broadcast_to(1.0 / ((opt["v0"] + nsj + 1 - d - 1) * c11), (K, S, d)).copy()
     else:
         W = np.broadcast_to(np.linalg.inv((opt["v0"] + nsj + 1 - d - 1) * c11), (K, S, d, d)).copy()
     alpha = opt["alpha0"] + NJ * np.ones(K)
     return Posterior(alpha=alpha, eta=eta, epsilon=eps, lam=lam, v=v, m=np.stack(centres), W=W,
                      W0mode="iid" if np.size(opt["W0"]) == 1 else "diag")
+
+
+# ----------------------------------------------------------------------------
+# 'wtkmeans' for every trial in batched device calls (include/vbhem_init.h)
+# ----------------------------------------------------------------------------
+WTK_OK, WTK_DEGENERATE, WTK_BAD = 0, 1, 2
+WTK_MAX_DIM, WTK_MAX_K, WTK_MAX_S = 16, 32, 16
+
+
+def wtkmeans_points_batched(base: BaseSet, mode: str = "r0", device=None):
+    """:func:`wtkmeans_points` with its loop over the base HMMs as batched tensor
+    operations on ``device`` (default: where ``base`` lies): (points [n][d], weights [n])
+    as float64 tensors there and the first base state's covariance as numpy.  Only the
+    batched initialisation uses it."""
+    dev = base.prior.device if device is None else torch.device(device)
+    ns = base.nstates.to(dev).long()
+    SB = base.SB
+    mask = torch.arange(SB, device=dev)[None, :] < ns[:, None]
+    p = base.prior.to(dev) * mask
+    if "0" in mode or "3" in mode:
+        A = base.A.to(dev) * mask[:, :, None] * mask[:, None, :]
+        step = lambda q: torch.bmm(q[:, None, :], A)[:, 0, :]
+        if "0" in mode:
+            for _ in range(50):
+                p = step(p)
+            wts = p
+        else:
+            wts = p.clone()
+            for _ in range(2):
+                p = step(p)
+                wts = wts + p
+            wts = wts / 3.0
+    elif "x" in mode:
+        wts = mask / ns[:, None].to(torch.float64)
+    else:
+        raise ValueError("unknown mode")
+    wv = wts[mask]
+    pts = base.centres.to(dev)[mask].contiguous()
+    return pts, (wv / wv.sum()).contiguous(), base.covars[0, 0].cpu().numpy()
+
+
+class WtkDeviceEngine:
+    """The two batched calls of include/vbhem_init.h on one device.  ``cluster`` keeps the
+    trials' labels on the device for ``states``; ``labels_of`` fetches one trial's."""
+
+    def __init__(self, device, chunk_trials=None):
+        self.dev = torch.device(device)
+        self.chunk = int(chunk_trials or 0)
+
+    def cluster(self, pts, w, K, j0, u):
+        """pts [n][d], w [n] on the device; j0 [R], u [R][max(K-1, 1)] numpy.  Returns
+        (labels handle, counts [R][K], status [R], iters [R][2]) -- numpy but the handle."""
+        from . import _capi
+        n, d = int(pts.shape[0]), int(pts.shape[1])
+        R = len(j0)
+        lib, dev = _capi.lib(), self.dev
+        self.pts, self.n, self.d, self.K, self.R = pts, n, d, int(K), R
+        tj = torch.as_tensor(np.asarray(j0, dtype=np.int32), device=dev)
+        tu = torch.as_tensor(np.ascontiguousarray(u, dtype=np.float64).reshape(R, max(K - 1, 1)), device=dev)
+        labels = torch.full((R, n), -1, dtype=torch.int32, device=dev)
+        counts = torch.zeros((R, K), dtype=torch.int32, device=dev)
+        status = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        iters = torch.zeros((R, 2), dtype=torch.int32, device=dev)
+        wb = lib.vbhem_wtk_cluster_workspace_bytes(n, d, K, R, self.chunk)
+        ws = _capi.workspace(wb, dev, 16)
+        p = _capi.ptr
+        _capi.check(lib.vbhem_wtk_cluster_batch(n, d, K, R, p(pts), p(w), p(tj), p(tu), self.chunk, p(labels),
+                                                p(counts), p(status), p(iters), p(ws), ws.numel(),
+                                                _capi.stream(dev)), "vbhem_wtk_cluster_batch")
+        return labels, counts.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
+
+    def labels_of(self, labels, r):
+        return labels[r].cpu().numpy()
+
+    def states(self, labels, S, trial, cluster, nmem, j0, u):
+        """The items (trial, cluster, nmem, j0, u [I][max(S-1, 1)]) over the labels of
+        ``cluster``.  Returns (centres [R][K][S][d], status [I], iters [I]) as numpy; only
+        the rows of OK items are meaningful."""
+        from . import _capi
+        lib, dev, I = _capi.lib(), self.dev, len(trial)
+        centres = torch.zeros((self.R, self.K, S, self.d), dtype=torch.float64, device=dev)
+        if I == 0:
+            return centres.cpu().numpy(), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        nm = np.asarray(nmem, dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(nm)])
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+        tt, tc, tn, tj = (t(a, np.int32) for a in (trial, cluster, nmem, j0))
+        to = t(off[:-1], np.int64)
+        tu = t(np.asarray(u, dtype=np.float64).reshape(I, max(S - 1, 1)), np.float64)
+        status = torch.full((I,), -1, dtype=torch.int32, device=dev)
+        iters = torch.zeros((I,), dtype=torch.int32, device=dev)
+        wb = lib.vbhem_wtk_states_workspace_bytes(int(off[-1]))
+        ws = _capi.workspace(wb, dev, 16)
+        p = _capi.ptr
+        _capi.check(lib.vbhem_wtk_states_batch(self.n, self.d, self.K, S, self.R, p(self.pts), p(labels), I, p(tt),
+                                               p(tc), p(tn), p(to), int(off[-1]), p(tj), p(tu), p(centres),
+                                               p(status), p(iters), p(ws), ws.numel(), _capi.stream(dev)),
+                    "vbhem_wtk_states_batch")
+        return centres.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
+
+
+def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_trials=None,
+                        engine=None, info: Optional[dict] = None) -> List[Posterior]:
+    """``[wtkmeans_init(base, opt, s, pts) for s in wtseeds]`` with the k-means of every
+    trial in two batched device calls (csrc/vbhem_wtk.hip): all trials' K-way clustering,
+    then the S-way k-means of every (trial, cluster) with more than S members.  The host
+    draws from the same generators in the same order -- PCG64(wtseed) for the first stage,
+    a fresh PCG64(wtseed + 1) per cluster with more than S members, makeAprior from
+    whichever of them wtkmeans_init would hold -- and reads the member counts between the
+    calls, because the second stage's first draw is an index into the members.  Clusters
+    with at most S members and empty clusters are filled in here as wtkmeans_init does;
+    a trial whose D2 total vanishes (the host's generator takes another branch there) is
+    replayed through wtkmeans_init.  ``engine``: a stand-in for :class:`WtkDeviceEngine`;
+    ``info``: a dict that receives the seconds of the parts (points, cluster, states: each
+    ends in a copy back to the host; host: the rest), the number of second-stage items and
+    the replayed trials."""
+    import time
+    t0 = time.perf_counter()
+    copt = clip_hyps(opt)
+    mode = copt.get("initopt_mode", "r0")
+    K, S = int(copt["K"]), int(copt["S"])
+    Kb, d = base.N, base.d
+    for name, val, lim in (("d", d, WTK_MAX_DIM), ("K", K, WTK_MAX_K), ("S", S, WTK_MAX_S)):
+        if val > lim:
+            raise ValueError(f"wtkmeans_init_batch: {name} = {val} exceeds the device limit {name} <= {lim}")
+    eng = engine if engine is not None else WtkDeviceEngine(device, chunk_trials)
+    dev = getattr(eng, "dev", torch.device("cpu"))
+    pts, w, c11 = wtkmeans_points_batched(base, mode, dev)
+    n = int(pts.shape[0])
+    t1 = time.perf_counter()
+    seeds = [int(s) for s in wtseeds]
+    R = len(seeds)
+    if R == 0:
+        return []
+    g1s = [np.random.Generator(np.random.PCG64(s)) for s in seeds]
+    j0 = np.array([g.integers(n) for g in g1s], dtype=np.int64)
+    u = np.array([[g.random() for _ in range(K - 1)] + [0.0] * (K == 1) for g in g1s])
+    t2 = time.perf_counter()
+    labels, counts, status, _ = eng.cluster(pts, w, K, j0, u)
+    t3 = time.perf_counter()
+    if (status == WTK_BAD).any():
+        raise ValueError("wtkmeans_init_batch: non-finite base-state means or weights")
+    g2s = list(g1s)
+    items = []
+    for r in range(R):
+        if status[r] != WTK_OK:
+            continue
+        for i in range(K):
+            cnt = int(counts[r, i])
+            if cnt > S:
+                g2s[r] = np.random.Generator(np.random.PCG64(seeds[r] + 1))
+                items.append((r, i, cnt, int(g2s[r].integers(cnt)),
+                              [g2s[r].random() for _ in range(S - 1)] + [0.0] * (S == 1)))
+    t4 = time.perf_counter()
+    cen, st2, _ = eng.states(labels, S, *[[it[q] for it in items] for q in range(5)])
+    t5 = time.perf_counter()
+    if (st2 == WTK_BAD).any():
+        raise ValueError("wtkmeans_init_batch: a second-stage item was refused")
+    replay = set(np.flatnonzero(status != WTK_OK).tolist())
+    replay.update(items[q][0] for q in np.flatnonzero(st2 != WTK_OK))
+    host_pts = None
+    posts = []
+    for r in range(R):
+        if r in replay:
+            if host_pts is None:
+                host_pts = (pts.cpu().numpy(), w.cpu().numpy(), c11)
+            posts.append(wtkmeans_init(base, opt, seeds[r], host_pts))
+            continue
+        centres = [None] * K
+        lab = None
+        for i in range(K):
+            cnt = int(counts[r, i])
+            if cnt > S:
+                centres[i] = cen[r, i]
+            elif cnt > 0:
+                if lab is None:
+                    lab = eng.labels_of(labels, r)
+                    host_pts = host_pts or (pts.cpu().numpy(), w.cpu().numpy(), c11)
+                mi = host_pts[0][lab == i]
+                centres[i] = np.concatenate([mi, np.repeat(mi[:1], S - mi.shape[0], 0)], 0)
+        posts.append(_wtk_posterior(copt, mode, Kb, d, base.covmode, centres, g2s[r], c11))
+    if info is not None:
+        total = time.perf_counter() - t0
+        info.update(points=t1 - t0, cluster=t3 - t2, states=t5 - t4, items=len(items), replayed=sorted(replay))
+        info["host"] = total - info["points"] - info["cluster"] - info["states"]
+    return posts
 
 
 # ----------------------------------------------------------------------------

@@ -1,0 +1,73 @@
+/*
+ * vbhem_init.h -- C-ABI of the batched 'wtkmeans' initialisation on MI355X
+ * (vbhemhmm_init.m:294-425 as h3m.py wtkmeans_init restates it): the k-means++ seeding with
+ * Lloyd updates (h3m.kmeans_pp) and the weighted k-means (my_weighted_kmeans.m,
+ * h3m.weighted_kmeans) of every TRIAL of a list in two calls.  Every random draw is an
+ * input, so the host keeps the generators and their order.
+ *
+ *   vbhem_wtk_cluster_batch  one workgroup per trial: kmeans_pp over all n points for K
+ *                            centres, then weighted_kmeans from them
+ *   vbhem_wtk_states_batch   one workgroup per ITEM = (trial, cluster) with more than S
+ *                            members: kmeans_pp over the cluster's members (in point order)
+ *                            for S centres
+ * The second call's first draw of an item is an index into the cluster's members, so the
+ * host reads counts between the calls.
+ *
+ * Layouts (row-major, DEVICE pointers; return codes and stream of vbhem_estep.h):
+ *   points:  x[n][d], weight[n]
+ *   draws:   j0[.]: the first centre, an index into the members (all points in the first
+ *            call); u[.][max(k - 1, 1)]: the uniform draw of centre c at [c - 1]
+ *   cluster: labels[R][n], counts[R][K], status[R], iters[R][2] (Lloyd passes, sweeps)
+ *   states:  trial[I], cluster[I], nmem[I] (the cluster's member count, as counts gave it),
+ *            off[I] (the item's first slot in the workspace: the exclusive prefix sums of
+ *            nmem, total_members their sum); centres[R][K][S][d]: the rows of the items;
+ *            status[I], iters[I]
+ * Status: VBHEM_WTK_OK; VBHEM_WTK_DEGENERATE: a D2 total of zero (fewer distinct points
+ * than centres), where the host's generator would take another branch; VBHEM_WTK_BAD: a
+ * non-finite coordinate or weight, or an index, count or slot out of range.  A trial or
+ * item that is not OK writes its status alone.
+ * Limits: d <= 16, K <= 32, S <= 16; beyond: VBHEM_ERR_UNSUPPORTED.
+ *
+ * Every sum, scan and tie is taken in a fixed order: a trial's or item's result depends on
+ * its own inputs only -- not on R, its place in the list or chunk_trials (trials per
+ * launch; 0: as many as fit VBHEM_WTK_DEFAULT_WORKSPACE bytes).
+ */
+#ifndef VBHEM_INIT_H
+#define VBHEM_INIT_H
+
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define VBHEM_WTK_OK 0
+#define VBHEM_WTK_DEGENERATE 1
+#define VBHEM_WTK_BAD 2
+
+#define VBHEM_WTK_MAX_DIM 16
+#define VBHEM_WTK_MAX_K 32
+#define VBHEM_WTK_MAX_S 16
+#define VBHEM_WTK_DEFAULT_WORKSPACE ((size_t)1 << 30)
+
+/* Workspace of a first-stage call (0 on invalid / unsupported sizes). */
+size_t vbhem_wtk_cluster_workspace_bytes(int n, int d, int K, int R, int chunk_trials);
+
+int vbhem_wtk_cluster_batch(int n, int d, int K, int R, const double *x_dev, const double *weight_dev,
+                            const int *j0_dev, const double *u_dev, int chunk_trials, int *labels_dev,
+                            int *counts_dev, int *status_dev, int *iters_dev, void *workspace_dev,
+                            size_t workspace_bytes, void *stream);
+
+/* Workspace of a second-stage call over items with total_members members in all. */
+size_t vbhem_wtk_states_workspace_bytes(long long total_members);
+
+int vbhem_wtk_states_batch(int n, int d, int K, int S, int R, const double *x_dev, const int *labels_dev, int I,
+                           const int *trial_dev, const int *cluster_dev, const int *nmem_dev,
+                           const long long *off_dev, long long total_members, const int *j0_dev,
+                           const double *u_dev, double *centres_dev, int *status_dev, int *iters_dev,
+                           void *workspace_dev, size_t workspace_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* VBHEM_INIT_H */
