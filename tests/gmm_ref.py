@@ -10,7 +10,11 @@ Inputs:
   (c) edge sizes: N = K + 1, N = 63, 64, 65 and 129 (the edges of a round of lanes), K = 8
       at dim = 2, start rows that include observation 0 and observation N - 1;
   (d) the planted ill-conditioned fit: 40 points from N([160, 210], 20^2) and one point at
-      [1e4, 1e4], K = 2, rows [40, 3].
+      [1e4, 1e4], K = 2, rows [40, 3];
+  (e) the corners of the kernel's buckets (corner_fits): (K, dim) = (4, 2), (4, 8), (8, 8),
+      (6, 4), (7, 5), (8, 3), (2, 1), (8, 1) on subjects drawn from K well-separated states,
+      3 fits each.  These are compared with the reference with NO fit left out: the tests
+      assert that compare_with_reference returns 0.
 
 Tolerances: the project's own for the batched EM, ll and the lls trajectory at 1e-9
 relative, parameters at post_err < 1e-8.  A fit may be left out of the comparison with
@@ -160,6 +164,26 @@ def edge_fits():
     fits.append((5, 8, np.random.default_rng(8).choice(200, 8, replace=False), 0.0))
     fits.append((5, 8, np.array([199, 0, 17, 33, 64, 65, 128, 63]), 0.0))
     return subj, fits
+
+
+# (K, dim) at the corners of the kernel's buckets: K = 4 and 8 fill KM, K * dim = 64 leaves
+# no spare lane, K * dim * dim = 512 is 8 rounds of the covariance loops
+CORNERS = [(4, 2), (4, 8), (8, 8), (6, 4), (7, 5), (8, 3), (2, 1), (8, 1)]
+
+
+def corner_fits(K, dim):
+    """A subject of 40 sequences of 1..12 steps from K states (R.states_subject) and 3 fits
+    from seeded start rows.  With these seeds every fit completes (one of K = 8, dim = 1 at
+    max_iter) and the reference agrees with itself on every fit when its observations are
+    permuted: no fit may be left out."""
+    key = ("corner", K, dim)
+    if key not in _cache:
+        lens = np.random.default_rng(7000).integers(1, 13, 40)
+        subj = [R.states_subject(7100 + 10 * K + dim, K, dim, lens)]
+        N = int(lens.sum())
+        rng = np.random.default_rng(7200)
+        _cache[key] = (subj, [(0, K, rng.choice(N, K, replace=False), 0.0) for _ in range(3)])
+    return _cache[key]
 
 
 def planted_subject():

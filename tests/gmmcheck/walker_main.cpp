@@ -1,8 +1,9 @@
 // tests/gmmcheck/walker_main.cpp -- TEST-ONLY stand-alone program: the serial walker of
 // csrc/vbhmm_gmm_run.h on seeded inputs, for a run under the address and undefined-behaviour
 // sanitizers on the CPU (`make gmm_sanitize`; plain C++, no device compiler).  It walks
-// every shape class the kernel has: KM = 4 and 8, dim = 2, 3 and 8, N at the edges of a
-// round of lanes and N = K + 1, start rows 0 and N - 1, the initial posterior, a fit that
+// every shape class the kernel has: KM = 4 and 8 with K = KM, dim = 1, 2, 3 and 8, N at the
+// edges of a round of lanes and N = K + 1, start rows 0 and N - 1, the initial posterior
+// (also under an unequal W0inv), a fit that
 // stops at max_iter, an ill-conditioned fit with its regularised refit, and bad fits.
 #include <cmath>
 #include <cstdio>
@@ -23,22 +24,22 @@ struct Lcg {
   double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
 };
 
-Hyper hyper_of(int dim) {
+Hyper hyper_of(int dim, bool diag) {
   Hyper h;
   h.alpha0 = h.epsilon0 = h.beta0 = 1.0;
   h.v0 = dim + 8.0;
   for (int a = 0; a < kMaxDim; ++a) {
     h.m0[a] = 180.0;
-    h.W0inv[a] = 1000.0;
+    h.W0inv[a] = diag ? 1000.0 / (1 + a) : 1000.0;
   }
   return h;
 }
 
 // mode 0: an ordinary fit; 1: max_iter = 2; 2: one far point among the start rows (ill-
 // conditioned), then the same rows with reg = 1e-10; 3: bad fits; 4: whatever status the
-// fit ends with (N = K + 1 collapses onto single points)
+// fit ends with (N = K + 1 collapses onto single points).  diag: W0inv is 1000 / (1 + a)
 template <int KM>
-int one_case(int K, int dim, int N, unsigned long long seed, int mode) {
+int one_case(int K, int dim, int N, unsigned long long seed, int mode, bool diag = false) {
   Lcg g{seed};
   std::vector<double> x((size_t)N * dim);
   for (int n = 0; n < N; ++n) {
@@ -49,7 +50,7 @@ int one_case(int K, int dim, int N, unsigned long long seed, int mode) {
   for (int k = 0; k < K; ++k) rows[k] = k == 0 ? N - 1 : k == 1 ? 0 : (int)((long long)k * N / K);
   if (mode == 2)
     for (int a = 0; a < dim; ++a) x[(size_t)(N - 1) * dim + a] = 1e4;
-  const Hyper h = hyper_of(dim);
+  const Hyper h = hyper_of(dim, diag);
   const int PL = vbhem::emrun::post_len(KM, dim), max_iter = mode == 1 ? 2 : 100;
   std::vector<double> prior(KM, -1.0), mean(KM * dim, -1.0), cov(KM * dim * dim, -1.0), lls(max_iter, 0.0),
       post(PL, -1.0), wp((size_t)N * KM), wl(N);
@@ -103,6 +104,10 @@ int main() {
   bad += one_case<4>(2, 2, 41, 10, 2);
   bad += one_case<4>(2, 2, 40, 11, 3);
   bad += one_case<8>(2, 2, 40, 12, 3);
+  bad += one_case<4>(4, 8, 300, 13, 0);
+  bad += one_case<8>(8, 1, 300, 14, 0);
+  bad += one_case<8>(8, 8, 600, 15, 0, true);
+  bad += one_case<4>(3, 2, 130, 16, 0, true);
   std::printf(bad ? "FAILED %d\n" : "walker OK\n", bad);
   return bad != 0;
 }

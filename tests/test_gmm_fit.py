@@ -31,6 +31,17 @@ def test_walker_matches_reference_in_higher_dimensions(vb, dim):
     assert all(g["status"] == G.CONVERGED for g in got)
 
 
+@pytest.mark.parametrize("K,dim", G.CORNERS)
+def test_walker_matches_reference_at_the_bucket_corners(vb, K, dim):
+    subj, fits = G.corner_fits(K, dim)
+    got = G.run_fits(subj, fits, dim)
+    assert all(g["status"] < G.ILL for g in got)
+    assert G.compare_with_reference(got, subj, fits, post_err, f"K{K}d{dim}") == 0
+    if K <= 4:      # the fit does not depend on the padding
+        for a, b in zip(got, G.run_fits(subj, fits, dim, KM=8)):
+            assert G.same_bits(a, b, KM_differs=True)
+
+
 def test_walker_edge_sizes(vb):
     subj, fits = G.edge_fits()
     got = G.run_fits(subj, fits, 2)

@@ -47,6 +47,37 @@ def test_kernels_match_walker_and_reference(vb):
     assert d5[0]["status"] == G.MAX_ITER and d5[0]["iters"] == 5
 
 
+@pytest.mark.parametrize("K,dim", G.CORNERS)
+def test_kernels_match_walker_and_reference_at_the_bucket_corners(vb, K, dim):
+    """K = KM, K * dim = 64 lanes, 8 rounds of the covariance loops: the device against the
+    walker and against gmm_fit_randsample itself, no fit left out."""
+    subj, fits = G.corner_fits(K, dim)
+    hv, _ = G.hyper_vector(R.options(dim))
+    dev = G.run_fits(subj, fits, dim, "device", hyper=hv)
+    host = G.run_fits(subj, fits, dim, "host", hyper=hv)
+    assert all(g["status"] < G.ILL for g in dev)
+    G.compare_runs(dev, host, post_err, f"K{K}d{dim}")
+    assert G.compare_with_reference(dev, subj, fits, post_err, f"K{K}d{dim}") == 0
+
+
+def test_initial_posterior_at_the_full_bucket_with_a_diagonal_W0(vb):
+    subj, fits = G.corner_fits(8, 8)
+    opt = R.options(8, W0=R.diag_W0(8))
+    hv, _ = G.hyper_vector(opt)
+    got = G.run_fits(subj, fits, 8, "device", hyper=hv, KM=8)
+    G.check_initial_posterior(got, subj, fits, opt, post_err, 8, "K8d8w")
+    assert all(g["status"] < G.ILL for g in got)
+
+
+def test_KM_independence_bitwise_at_dim_8(vb):
+    subj, fits = G.corner_fits(4, 8)
+    hv, _ = G.hyper_vector(R.options(8))
+    four = G.run_fits(subj, fits, 8, "device", hyper=hv, KM=4)
+    eight = G.run_fits(subj, fits, 8, "device", hyper=hv, KM=8)
+    for i, (a, b) in enumerate(zip(four, eight)):
+        assert a["status"] < G.ILL and G.same_bits(a, b, KM_differs=True), i
+
+
 def test_initial_posterior_on_the_device(vb):
     subj, fits, _ = G.demo_fits()
     fits = fits[:24] + fits[72:]

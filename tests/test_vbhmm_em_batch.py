@@ -1,7 +1,8 @@
 """The run routines of the batched VB-HMM EM (csrc/vbhmm_em_run.h) on the host: the
 serial walker of tests/vbhmmemcheck against oracle/vbhmm_em_oracle.em(fb_fn='c'), which
-restates vbhmm_em.m + vbhmm_em_lb.m loop for loop.  Inputs (a), (b), (c) and the
-iteration-count condition are described in tests/vbhmm_em_batch_ref.py.  Tolerances are
+restates vbhmm_em.m + vbhmm_em_lb.m loop for loop.  Inputs (a) .. (e) and the
+iteration-count condition are described in tests/vbhmm_em_batch_ref.py; the cases of (d)
+and (e), the corners of the kernels' buckets, are compared with no run left out.  Tolerances are
 the project's: rtol 1e-9 on bound trajectories and post_err < 1e-8 on posteriors
 (tests/test_vbhmm_em.py), stat_err < 1e-10 on statistics (RTOL_PAIRS).
 """
@@ -18,15 +19,23 @@ def _input(name):
         return R.runs_a() + (R.options(),)
     if name == "b":
         return R.runs_b() + (R.options(),)
-    return R.runs_c(3) + (R.options(3),)
+    if name == "c3":
+        return R.runs_c(3) + (R.options(3),)
+    return R.corner_input(name)
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c3"])
+CORNERS = R.NAMES_D + R.NAMES_E
+
+
+@pytest.mark.parametrize("name", ["a", "b", "c3"] + CORNERS)
 def test_host_walker_matches_oracle(vb, vo, name):
     subj, runs, opt = _input(name)
     ref = R.oracle_runs(name, subj, runs, opt)
     got = R.run_check(subj, runs, opt, "host")
-    R.compare_with_oracle(got, ref, opt, post_err, name)
+    excluded = R.compare_with_oracle(got, ref, opt, post_err, name)
+    if name in CORNERS:
+        assert not any(R.near_threshold(r["LLs"], opt["minDiff"]) for r in ref), name
+        assert excluded == 0, name
     # the posterior at the last E-step: the oracle stopped one M-step earlier
     # (a): every ninth run (each (K, trial) pattern once); (b): one run per K; (c): all
     step = {"a": 9, "b": 3}.get(name, 1)
@@ -39,7 +48,7 @@ def test_host_walker_matches_oracle(vb, vo, name):
             assert post_err(got[i]["varpar_estep"][k], est[k]) < 1e-8, (name, i, k)
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c3"])
+@pytest.mark.parametrize("name", ["a", "b", "c3"] + CORNERS)
 def test_first_iteration_statistics(vb, vo, name):
     subj, runs, opt = _input(name)
     pick = list(range(0, len(runs), 9)) if name == "a" else list(range(len(runs)))
@@ -51,6 +60,21 @@ def test_first_iteration_statistics(vb, vo, name):
         for k in ("Nk1", "Nk", "M", "xbar", "t1_S"):
             assert stat_err(g[k], ref[k]) < RTOL_PAIRS, (name, s, K, k)
         assert abs(g["LLs"][0] - ref["L"]) <= RTOL_PAIRS * abs(ref["L"]), (name, s, K)
+    if name == "d8x1":       # the run with a far component: its state is empty
+        assert 1e-50 <= got[3]["Nk1"][0] <= got[3]["Nk"][0] < 1e-40
+
+
+def test_empty_sequences_change_no_bit(vb):
+    """A subject with empty sequences (first, last, two adjacent) gives the bits of the
+    same subject without them."""
+    subj, runs, opt = R.corner_input("e0")
+    assert [n for n, a in enumerate(subj[0]) if a.shape[0] == 0] == list(R.EMPTY_AT)
+    dense = R.without_empty(subj)
+    assert len(dense[0]) == len(subj[0]) - len(R.EMPTY_AT)
+    a = R.run_check(subj, runs, opt, "host")
+    b = R.run_check(dense, runs, opt, "host")
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert R.same_bits(x, y), i
 
 
 def test_unstable_run_is_contained(vb):

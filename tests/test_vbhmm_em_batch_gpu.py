@@ -1,8 +1,12 @@
 """The batched VB-HMM EM on the GPU (csrc/vbhmm_em.hip): vbhmm_em_batch against the
 oracle and against the host walker of the same routines, bitwise independence of a run
-from its position and from the launch chunking, NaN containment, vbhmm_em_gamma against
-vbhmm_fb, and the engine="fused" path of vbhmm_learn_batch / learn_hyps_batch against
-engine="loop".  Inputs and conditions: tests/vbhmm_em_batch_ref.py.
+from its position, from the launch chunking and from KM, NaN containment, vbhmm_em_gamma
+against vbhmm_fb and the C forward-backward, and the engine="fused" path of
+vbhmm_learn_batch / learn_hyps_batch against engine="loop".  The cases of inputs (d) and
+(e) sit at the corners of the kernel's buckets (K = KM, K * dim = 64 lanes, 8 rounds of
+the covariance loop, a third round of sequences, empty sequences) and are compared with
+the oracle directly, with no run left out.  Inputs and conditions:
+tests/vbhmm_em_batch_ref.py.
 """
 import numpy as np
 import pytest
@@ -44,6 +48,69 @@ def test_batch_matches_oracle_and_host_walker(vb, vo, name):
 def test_edge_subjects_match_host_walker(vb, dim):
     subj, runs = R.runs_c(dim)
     _vs_host(subj, runs, R.options(dim), f"c{dim}")
+
+
+CORNERS = R.NAMES_D + R.NAMES_E
+
+
+@pytest.mark.parametrize("name", CORNERS)
+def test_bucket_corners_match_oracle_and_host_walker(vb, vo, name):
+    """The device against the walker AND against the oracle itself: what walker and
+    kernel share cannot hide behind their agreement."""
+    subj, runs, opt = R.corner_input(name)
+    dev = _vs_host(subj, runs, opt, name)
+    ref = R.oracle_runs(name, subj, runs, opt)
+    assert not any(R.near_threshold(r["LLs"], opt["minDiff"]) for r in ref), name
+    assert R.compare_with_oracle(dev, ref, opt, post_err, name) == 0, name
+    for i, (s, K, g) in enumerate(runs):      # the posterior at the last E-step
+        est = R.oracle_estep_posterior(subj[s], K, opt, g, ref[i]["iters"])
+        for k in R.POST_KEYS:
+            assert post_err(dev[i]["varpar_estep"][k], est[k]) < 1e-8, (name, i, k)
+    d1 = R.run_check(subj, runs, opt, "device", max_iter=1)
+    for i, (d, (s, K, g)) in enumerate(zip(d1, runs)):
+        first = R.oracle_first_iteration(subj[s], K, opt, g)
+        assert d["iters"] == 1 and d["status"] == 1, (name, i)
+        for k in ("Nk1", "Nk", "M", "xbar", "t1_S"):
+            assert stat_err(d[k], first[k]) < RTOL_PAIRS, (name, i, k)
+        assert abs(d["LLs"][0] - first["L"]) <= RTOL_PAIRS * abs(first["L"]), (name, i)
+
+
+def test_empty_sequences_change_no_bit_on_the_device(vb):
+    subj, runs, opt = R.corner_input("e0")
+    a = R.run_check(subj, runs, opt, "device")
+    b = R.run_check(R.without_empty(subj), runs, opt, "device")
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert R.same_bits(x, y), i
+
+
+@pytest.mark.parametrize("name", ["d4x2", "d4x8", "d3x2w", "c8", "e0"])
+def test_result_does_not_depend_on_KM_on_the_device(vb, name):
+    """The contract of csrc/vbhmm_em.hip: a K <= 4 run gives the same bits under KM = 4 and
+    KM = 8 (Python takes KM from the largest K of the whole list)."""
+    subj, runs, opt = R.runs_c(8) + (R.options(8),) if name == "c8" else R.corner_input(name)
+    assert max(r[1] for r in runs) <= 4
+    four = R.run_check(subj, runs, opt, "device", KM=4)
+    eight = R.run_check(subj, runs, opt, "device", KM=8)
+    for i, (x, y) in enumerate(zip(four, eight)):
+        assert R.same_bits(x, y, KM_differs=True), (name, i)
+
+
+def test_position_independence_bitwise_at_the_full_bucket(vb):
+    """K = 8 and K = 5 runs at dim = 8 of a larger and a smaller subject, mixed: with one
+    run per launch every launch reuses slot 0, a larger run before a smaller one."""
+    subj, runs, opt = R.runs_mixed()
+    base = R.run_check(subj, runs, opt, "device")
+    one = R.run_check(subj, runs, opt, "device", chunk_runs=1)
+    two = R.run_check(subj, runs, opt, "device", chunk_runs=2)
+    rev = R.run_check(subj, runs[::-1], opt, "device", chunk_runs=1)
+    for i in range(len(runs)):
+        assert R.same_bits(base[i], one[i]), i
+        assert R.same_bits(base[i], two[i]), i
+        assert R.same_bits(base[i], rev[len(runs) - 1 - i]), i
+    host = R.run_check(subj, runs, opt, "host")
+    for i, (d, h) in enumerate(zip(base, host)):
+        assert d["iters"] == h["iters"] and d["status"] == h["status"], i
+        np.testing.assert_allclose(d["LLs"], h["LLs"], rtol=1e-9, err_msg=f"mixed run {i}")
 
 
 def test_position_independence_bitwise(vb):
@@ -92,6 +159,30 @@ def test_gamma_matches_vbhmm_fb(vb):
             assert np.max(np.abs(g - ref[:, n, :T])) <= 1e-12 * np.max(np.abs(ref[:, n, :T]))
 
 
+@pytest.mark.parametrize("name", ["d8x8", "d4x8", "e0"])
+def test_gamma_matches_the_c_forward_backward(vb, vo, name):
+    """Gamma-only mode at the full buckets and on the subject with empty sequences,
+    against the C restatement of vbhmm_fb_mex.c on the CPU."""
+    from vbhem_amd import vbhmm
+    from vbhem_amd.vbhmm_em import vbhmm_em_gamma
+    subj, runs, opt = R.corner_input(name)
+    dim = len(opt["mu0"])
+    sb = vbhmm.SubjectBatch(subj, dim, DEV)
+    items = [(0, vp) for vp in R.initial_posteriors(subj, runs, opt)]
+    got = vbhmm_em_gamma(sb, items)
+    assert len(got) == len(items)
+    for (s, vp), gam in zip(items, got):
+        ref = vo.c_vbhmm_fb(subj[s], vp)["gamma"].transpose(2, 1, 0)         # [K, N, maxT]
+        assert len(gam) == len(subj[s])
+        for n, g in enumerate(gam):
+            T = subj[s][n].shape[0]
+            assert g.shape == (ref.shape[0], T), (name, n)
+            if T:
+                assert np.max(np.abs(g - ref[:, n, :T])) <= 1e-12 * np.max(np.abs(ref[:, n, :T])), (name, n)
+    if name == "e0":
+        assert [n for n, g in enumerate(got[0]) if g.shape[1] == 0] == list(R.EMPTY_AT)
+
+
 @pytest.fixture(scope="module")
 def engines(vb):
     from vbhem_amd.vbhmm_em import vbhmm_learn_batch
@@ -103,8 +194,24 @@ def engines(vb):
 
 
 def test_learn_batch_engines_agree(vb, engines):
+    _engines_agree(vb, *engines)
+
+
+def test_learn_batch_engines_agree_in_the_larger_bucket(vb):
+    """dim = 3, K = 4 and 5 in one call (KM = 8), injected GMMs, 2 trials, 3 subjects."""
+    from vbhem_amd.vbhmm_em import vbhmm_learn_batch
+    rng = np.random.default_rng(81)
+    subj = [R.states_subject(82 + s, 5, 3, rng.integers(3, 10, 14 + 3 * s)) for s in range(3)]
+    gmms = [{K: R.gmm_trials(d, K, 2, seed=90 + K) for K in (4, 5)} for d in subj]
+    opt = R.options(3, numtrials=2)
+    loop = vbhmm_learn_batch(subj, [4, 5], opt, device=DEV, gmms=gmms)
+    fused = vbhmm_learn_batch(subj, [4, 5], opt, device=DEV, gmms=gmms, engine="fused")
+    _engines_agree(vb, subj, loop, fused)
+
+
+def _engines_agree(vb, subj, loop, fused):
     from vbhem_amd.vbhmm_em import vbhmm_remove_empty
-    subj, (hl, Ll), (hf, Lf) = engines
+    (hl, Ll), (hf, Lf) = loop, fused
     np.testing.assert_allclose(Lf, Ll, rtol=1e-9)
     for s, (a, b) in enumerate(zip(hl, hf)):
         assert a["model_bestK"] == b["model_bestK"], s
@@ -121,7 +228,7 @@ def test_learn_batch_engines_agree(vb, engines):
             np.testing.assert_allclose(g.sum(0), 1.0, rtol=1e-12)
     base = vb.hmms_to_h3m_hem([vbhmm_remove_empty(h, 1e-3) for h in hf], vb.COV_FULL, True)
     ref = vb.hmms_to_h3m_hem([vbhmm_remove_empty(h, 1e-3) for h in hl], vb.COV_FULL, True)
-    assert base.N == ref.N == 10
+    assert base.N == ref.N == len(subj)
 
 
 def _lhb_setup(engine):

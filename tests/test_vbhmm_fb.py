@@ -39,6 +39,7 @@ def make_fb_case(N=6, K=3, dim=2, maxT=9, seed=0, empty=True):
 FB_SHAPES = [  # (name, N, K, dim, maxT)
     ("eye", 12, 3, 2, 15), ("K1", 5, 1, 2, 6), ("T1", 6, 4, 2, 1), ("dim1", 7, 3, 1, 9),
     ("dim5", 5, 5, 5, 8), ("K8", 9, 8, 2, 20), ("K16", 4, 16, 3, 12), ("long", 3, 4, 2, 300),
+    ("K4d8", 6, 4, 8, 10), ("K8d8", 6, 8, 8, 10), ("K16d8", 4, 16, 8, 12), ("K9d4", 5, 9, 4, 9),
 ]
 
 

@@ -1,8 +1,9 @@
 // tests/vbhmmemcheck/walker_main.cpp -- TEST-ONLY stand-alone program: the serial walker of
 // csrc/vbhmm_em_run.h on seeded inputs, for a run under the address and undefined-behaviour
 // sanitizers on the CPU (`make vbhmmem_sanitize`; plain C++, no device compiler).  It
-// walks every shape class the kernel has: KM = 4 and 8, dim = 2 and 8, 70 sequences with
-// lengths 1..49 (T = 1 included), a single sequence, and an unstable run.
+// walks every shape class the kernel has: KM = 4 and 8 with K = KM, dim = 1, 2 and 8, 70
+// sequences with lengths 1..49 (T = 1 included), 130 short sequences, a single sequence,
+// empty sequences (first, last, two adjacent), an unequal W0inv, and an unstable run.
 #include <cmath>
 #include <cstdio>
 #include <vector>
@@ -22,11 +23,17 @@ struct Lcg {
   double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
 };
 
+// empties: sequences 0, N / 2, N / 2 + 1 and N - 1 have no observation; diag: W0inv is
+// 1000 / (1 + a) instead of 1000
 template <int KM>
-int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool break_W) {
+int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool break_W, bool empties = false,
+             bool diag = false) {
   Lcg g{seed};
   std::vector<int> off(N + 1, 0);
-  for (int n = 0; n < N; ++n) off[n + 1] = off[n] + (n == 0 ? 1 : 1 + (int)(g.uni() * maxlen));
+  for (int n = 0; n < N; ++n) {
+    const bool none = empties && (n == 0 || n == N / 2 || n == N / 2 + 1 || n == N - 1);
+    off[n + 1] = off[n] + (none ? 0 : n == 0 ? 1 : 1 + (int)(g.uni() * maxlen));
+  }
   const int obs = off[N];
   std::vector<double> x((size_t)obs * dim);
   for (int p = 0; p < obs; ++p) {
@@ -38,7 +45,7 @@ int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool br
   h.v0 = dim + 8.0;
   for (int a = 0; a < kMaxDim; ++a) {
     h.m0[a] = 180.0;
-    h.W0inv[a] = 1000.0;
+    h.W0inv[a] = diag ? 1000.0 / (1 + a) : 1000.0;
   }
   const int PL = post_len(KM, dim), SL = stats_len(KM, dim);
   std::vector<double> post(PL, 1.0), est(PL), st(SL), LLs(30, 0.0);
@@ -59,8 +66,8 @@ int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool br
   const Work<KM> w{gm.data(), lr.data(), cs.data(), mx.data(), sq.data()};
   const Subject s{N, off.data(), x.data()};
   const RunResult r = run_serial<KM>(K, dim, s, h, 30, 1e-5, post.data(), est.data(), st.data(), LLs.data(), w);
-  std::printf("KM=%d K=%d dim=%d N=%d obs=%d: LL=%.12g iters=%d status=%d\n", KM, K, dim, N, obs, r.LL, r.iters,
-              r.status);
+  std::printf("KM=%d K=%d dim=%d N=%d obs=%d%s%s: LL=%.12g iters=%d status=%d\n", KM, K, dim, N, obs,
+              empties ? " empties" : "", diag ? " diag" : "", r.LL, r.iters, r.status);
   if (break_W) return !(r.status == kUnstable && r.iters == 1 && std::isinf(r.LL));
   return !(std::isfinite(r.LL) && r.status != kUnstable && r.iters >= 1);
 }
@@ -76,6 +83,12 @@ int main() {
   bad += one_case<8>(8, 8, 40, 12, 5, false);
   bad += one_case<4>(2, 2, 1, 9, 6, false);
   bad += one_case<4>(2, 2, 30, 5, 7, true);
+  bad += one_case<4>(4, 8, 40, 12, 8, false);
+  bad += one_case<8>(8, 1, 40, 12, 9, false);
+  bad += one_case<4>(3, 2, 130, 3, 10, false);
+  bad += one_case<4>(3, 2, 14, 8, 11, false, true);
+  bad += one_case<8>(8, 8, 40, 12, 12, false, true, true);
+  bad += one_case<4>(3, 2, 30, 5, 13, false, false, true);
   std::printf(bad ? "FAILED %d\n" : "walker OK\n", bad);
   return bad != 0;
 }
