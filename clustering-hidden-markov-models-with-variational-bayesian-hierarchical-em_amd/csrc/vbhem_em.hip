@@ -25,34 +25,21 @@
 #include "vbhem_em.h"
 #include "vbhem_em_dev.h"
 #include "vbhem_internal.h"
+#include "vbhem_special.h"
 
 namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 
-// digamma for x > 0: psi(x) = psi(x + n) - sum_{k<n} 1/(x + k), then the
-// asymptotic expansion ln x - 1/(2x) - sum B_2k / (2k x^2k) at x >= 8.
-double psi(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : std::nan("");
-  double acc = 0.0;
-  while (x < 8.0) {
-    acc -= 1.0 / x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
-      r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
-  return acc + std::log(x) - 0.5 * r - series;
-}
+using vbhem::psi_recur;  // the one-division-per-step digamma (vbhem_special.h)
 
-// sum_{q=1..d} psi((v + 1 - q) / 2) (step_fc.m:136): the arguments are two chains
+// sum_{q=1..d} psi_recur((v + 1 - q) / 2) (step_fc.m:136): the arguments are two chains
 // v/2, v/2 - 1, ... and (v-1)/2, (v-1)/2 - 1, ...; one psi per chain, the rest by
-// psi(x - 1) = psi(x) - 1/(x - 1)
+// psi_recur(x - 1) = psi_recur(x) - 1/(x - 1)
 double psi_sum_half(double v, int d) {
   double acc = 0.0;
   for (int c = 0; c < 2 && c < d; ++c) {
-    double x = 0.5 * (v - c), p = psi(x);
+    double x = 0.5 * (v - c), p = psi_recur(x);
     for (int q = c; q < d; q += 2) {
       acc += p;
       x -= 1.0;
@@ -212,19 +199,19 @@ int vbhem_em_prelude(const vbhem_post_t *post, double *logA, double *logPi, doub
       const double *eps = post->epsilon + ks * S;
       double es = 0.0;
       for (int s2 = 0; s2 < S; ++s2) es += eps[s2];
-      const double pes = psi(es);
-      for (int s2 = 0; s2 < S; ++s2) logA[ks * S + s2] = psi(eps[s2]) - pes;
+      const double pes = psi_recur(es);
+      for (int s2 = 0; s2 < S; ++s2) logA[ks * S + s2] = psi_recur(eps[s2]) - pes;
     }
     double ets = 0.0;
     for (int s = 0; s < S; ++s) ets += post->eta[(size_t)k * S + s];
-    const double pet = psi(ets);
+    const double pet = psi_recur(ets);
     for (int s = 0; s < S; ++s)
-      logPi[(size_t)k * S + s] = psi(post->eta[(size_t)k * S + s]) - pet;
+      logPi[(size_t)k * S + s] = psi_recur(post->eta[(size_t)k * S + s]) - pet;
   }
   double as = 0.0;
   for (int k = 0; k < K; ++k) as += post->alpha[k];
-  const double pas = psi(as);
-  for (int k = 0; k < K; ++k) logOmega[k] = psi(post->alpha[k]) - pas;
+  const double pas = psi_recur(as);
+  for (int k = 0; k < K; ++k) logOmega[k] = psi_recur(post->alpha[k]) - pas;
   return VBHEM_OK;
 }
 
@@ -406,11 +393,11 @@ int vbhem_em_lower_bound_derivs(const vbhem_post_t *post, const vbhem_em_opt_t *
   for (size_t x = 0; x < (size_t)K * S; ++x) { sPi += logPi[x]; sL += logLambdaTilde[x]; }
   for (size_t x = 0; x < (size_t)K * S * S; ++x) sA += logA[x];
   double *g = dLL;
-  g[0] = K * psi(K * a0) - K * psi(a0) + sO;                              // alpha0
-  g[1] = K * (S * psi(S * e0) - S * psi(e0)) + sPi;                       // eta0
-  g[2] = (double)K * S * (S * psi(S * ep0) - S * psi(ep0)) + sA;          // epsilon0
+  g[0] = K * psi_recur(K * a0) - K * psi_recur(a0) + sO;                              // alpha0
+  g[1] = K * (S * psi_recur(S * e0) - S * psi_recur(e0)) + sPi;                       // eta0
+  g[2] = (double)K * S * (S * psi_recur(S * ep0) - S * psi_recur(ep0)) + sA;          // epsilon0
   double sp = 0.0;
-  for (int q = 1; q <= d; ++q) sp += psi(0.5 * (v0 + 1 - q));
+  for (int q = 1; q <= d; ++q) sp += psi_recur(0.5 * (v0 + 1 - q));
   g[3] = (double)K * S * (0.5 * logdetW0inv - (d / 2.0) * std::log(2.0) - 0.5 * sp) + 0.5 * sL;  // v0
   const int nW = opt->W0_len;
   double *gW = g + 5, *gm = g + 5 + nW;

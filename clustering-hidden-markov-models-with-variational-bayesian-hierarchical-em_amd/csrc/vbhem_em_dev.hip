@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "vbhem_em_dev.h"
+#include "vbhem_special.h"
 
 namespace vbhem {
 
@@ -37,42 +38,6 @@ namespace {
 constexpr double kPiD = 3.14159265358979323846;
 constexpr double kLn2D = 0.69314718055994530942;
 constexpr int kWaves = 4;  // waves (cluster states) per block
-
-// digamma for x > 0 (the host routine's series): psi(x) = psi(x + n) -
-// sum_{i<n} 1/(x + i) with x + n >= 8, the sum as ONE division of a running
-// numerator / denominator (fp64 division is a long dependent sequence on the GPU),
-// then ln z - 1/(2z) - sum B_2k / (2k z^2k)
-__device__ double psi_dev(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : __builtin_nan("");
-  double num = 0.0, den = 1.0;
-  while (x < 8.0) {  // num / den = sum 1/(x_i) so far
-    num = fma(num, x, den);
-    den *= x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
-      r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
-  return log(x) - 0.5 * r - series - num / den;
-}
-
-// log Gamma for x > 0: lgamma(x) = lgamma(x + n) - log(prod_{i<n} (x + i)) with
-// z = x + n >= 10, then Stirling's series (z - 1/2) ln z - z + ln(2 pi)/2 +
-// sum B_2k / (2k (2k - 1) z^(2k-1)) through z^-15 (next term < 3e-18 at z = 10)
-__device__ double lgamma_dev(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : __builtin_nan("");
-  double prod = 1.0;
-  while (x < 10.0) {
-    prod *= x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 -
-      r2 * (691.0 / 360360 - r2 * (1.0 / 156 - r2 * (3617.0 / 122400))))))));
-  return (x - 0.5) * log(x) - x + 0.91893853320467274178 + series - log(prod);
-}
 
 __device__ __forceinline__ void wsync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -227,7 +192,7 @@ __global__ __launch_bounds__(64 * kWaves) void em_iter_kernel(const EmDevArgs a,
       xg = lane == 16 ? ps : lane == 17 ? e : lane == 18 ? es : al;
       lg_on = lane < 18 || s == 0;
     }
-    const double lgx = lg_on ? lgamma_dev(xg) : 0.0;
+    const double lgx = lg_on ? lgamma_stirling(xg) : 0.0;
     // quadratic forms over the lanes = entries (x, z)
     double t_mwm = 0.0, t_tr = 0.0;
     for (int x = lane; x < d * d; x += 64) {
@@ -384,7 +349,7 @@ __global__ __launch_bounds__(64 * kWaves) void em_iter_kernel(const EmDevArgs a,
     xp = lane == 16 ? es : lane == 17 ? eta_ks : lane == 18 ? sum_eta : lane == 19 ? alpha_k : sa;
     p_on = lane < 19 || s == 0;
   }
-  const double pl = p_on ? psi_dev(xp) : 0.0;
+  const double pl = p_on ? psi_onediv(xp) : 0.0;
   const double t1 = wsum(lane < d ? pl : 0.0);
   const double pes = __shfl(pl, 16, 64), pet = __shfl(pl, 17, 64), pst = __shfl(pl, 18, 64);
   const double pal = __shfl(pl, 19, 64), psa = __shfl(pl, 20, 64);
@@ -443,7 +408,7 @@ __global__ __launch_bounds__(64 * kWaves) void em_iter_kernel(const EmDevArgs a,
         const double Lt5 =
             0.5 * q[0] + (double)K * S * a.logB0 + 0.5 * (v0 - d - 1) * q[1] - 0.5 * q[2];
         const double Lt6 = a.logCalpha0 + (a0 - 1) * q[9];
-        const double Lt8 = (lgamma_dev(q[12]) - q[11]) + q[10];
+        const double Lt8 = (lgamma_stirling(q[12]) - q[11]) + q[10];
         const double Lt10 = 0.5 * q[3] - 0.5 * d * S * K - q[4];
         *L_out = st.Lt1 + q[8] + Lt3 + Lt4 + Lt5 + Lt6 - st.Lt7 - Lt8 - q[5] - Lt10;
         *a.ticket = 0;  // ready for the next launch

@@ -16,25 +16,10 @@
 
 #include "vbhem_estep.h"
 #include "vbhem_internal.h"
+#include "vbhem_special.h"
 
 namespace vbhem {
 namespace {
-
-// digamma for x > 0: recurrence to x >= 8, then ln x - 1/(2x) - sum B_2k / (2k x^2k)
-// (the host loop's psi, vbhem_em.hip)
-__device__ double psi_dev(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : __builtin_nan("");
-  double acc = 0.0;
-  while (x < 8.0) {
-    acc -= 1.0 / x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
-      r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
-  return acc + log(x) - 0.5 * r - series;
-}
 
 struct H3mArgs {
   int N, SB, d, covmode, use_post;
@@ -97,9 +82,9 @@ __global__ __launch_bounds__(kH3mThreads) void hmms_to_h3m_kernel(H3mArgs p) {
       sa += al[t];
       se += ep[t];
     }
-    p.prior[is] = exp(psi_dev(al[s]) - psi_dev(sa));
-    const double pse = psi_dev(se);
-    for (int t = 0; t < SB; ++t) Ar[t] = t < ns ? exp(psi_dev(ep[t]) - pse) : 0.0;
+    p.prior[is] = exp(psi_recur(al[s]) - psi_recur(sa));
+    const double pse = psi_recur(se);
+    for (int t = 0; t < SB; ++t) Ar[t] = t < ns ? exp(psi_recur(ep[t]) - pse) : 0.0;
     const double be = p.beta[is];
     infl = (be + 1.0) / be;
   } else {

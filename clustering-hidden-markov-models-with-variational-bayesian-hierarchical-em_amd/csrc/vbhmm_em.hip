@@ -1,11 +1,14 @@
 // vbhmm_em.hip -- the fused, batched VB-HMM EM (include/vbhmm_em.h): the whole EM of every
 // run of a list in one call, no host round trip inside the loop.  The arithmetic of a run
-// is vbhmm_em_run.h, shared with the host check build.
+// AND its schedule (run_em) are vbhmm_em_run.h, shared with the host check build; the
+// kernel's own are the check of the run against the workspace sizes, the carving of the
+// slot (or of the caller's gamma array) and the run's LL / iters / status.
 //
 // vbhmm_em_kernel<KM>: a workgroup is ONE wavefront and owns ONE run (run = chunk start +
 // blockIdx.x) for its whole EM; the run's small state (posterior, prelude, statistics,
 // bound terms: Run<KM>) lives in the workgroup's LDS, its per-observation and per-sequence
-// records in the workspace slot of the workgroup.  Per iteration:
+// records in the workspace slot of the workgroup.  run_em with a unit per lane (WaveLanes)
+// is, per iteration:
 //   prelude   a lane per state
 //   phase A   a lane per sequence, in rounds of 64 sequences (fb_sequence): gamma, logrho,
 //             c_t, max_t to the slot, the sequence's record (sum xi, phi, sum gamma logrho,
@@ -29,6 +32,7 @@
 
 #include "vbhem_estep.h"
 #include "vbhem_internal.h"
+#include "vbhmm_batch_launch.h"
 #include "vbhmm_em.h"
 #include "vbhmm_em_run.h"
 
@@ -82,7 +86,6 @@ __global__ __launch_bounds__(64, KM == 4 ? 2 : 1) void vbhmm_em_kernel(const EmA
     return;
   }
   const Subject s{N, p.offsets + n0, p.x};
-  const int base = s.off[0];
   double *slot = p.ws + (size_t)blockIdx.x * p.slot;
   Work<KM> w;
   w.gamma = gamma_only ? p.gamma_out + (size_t)p.gamma_row[run] * KM : slot;
@@ -91,110 +94,35 @@ __global__ __launch_bounds__(64, KM == 4 ? 2 : 1) void vbhmm_em_kernel(const EmA
   w.mxs = w.cs + p.max_obs;
   w.seq = w.mxs + p.max_obs;
 
-  const int PL = post_len(KM, dim), SL = stats_len(KM, dim);
-  const double *pin = p.post + (size_t)run * PL;
-  for (int x = lane; x < PL; x += 64) r.post[x] = pin[x];
-  for (int x = lane; x < SL; x += 64) r.stats[x] = 0.0;
-  if (lane == 0) {
-    r.K = K;
-    r.dim = dim;
-    r.L = r.lastL = -1.7976931348623157e308;
-    r.flags = 0;
-  }
-  __syncthreads();
-
-  int it = 1;
-  for (; it <= p.max_iter; ++it) {
-    if (lane < K) prelude_state(r, lane);
-    __syncthreads();
-    for (int n = lane; n < N; n += 64) {
-      const int q = s.off[n] - base, T = s.off[n + 1] - s.off[n];
-      fb_sequence<KM>(r, s.x + (size_t)s.off[n] * dim, T, w.gamma + (size_t)q * KM, w.logrho + (size_t)q * KM,
-                      w.cs + q, w.mxs + q, w.seq + (size_t)n * seq_len(KM));
-    }
-    if (gamma_only) break;
-    __syncthreads();
-    if (lane < K) stat_counts(r, s, w, lane);
-    if (lane < KM * KM && lane / KM < K && lane % KM < K) stat_trans(r, s, w, lane / KM, lane % KM);
-    __syncthreads();
-    if (lane < K * dim) stat_mean(r, s, w, lane / dim, lane % dim);
-    __syncthreads();
-    for (int e = lane; e < K * dim * dim; e += 64) stat_cov(r, s, w, e / (dim * dim), (e / dim) % dim, e % dim);
-    __syncthreads();
-    if (lane < K) bound_state(r, p.h, lane);
-    __syncthreads();
-    if (lane == 0) {
-      loop_control(r, bound_total(r, p.h, N, w.seq), it, p.max_iter, p.min_diff);
-      if (p.LLs) p.LLs[(size_t)run * p.max_iter + (it - 1)] = r.L;
-    }
-    __syncthreads();
-    const int flags = r.flags;
-    if (flags & 1) {  // the last E-step: its posterior and statistics
-      if (p.post_estep)
-        for (int x = lane; x < PL; x += 64) p.post_estep[(size_t)run * PL + x] = r.post[x];
-      if (p.stats)
-        for (int x = lane; x < SL; x += 64) p.stats[(size_t)run * SL + x] = r.stats[x];
-    }
-    if (flags & 4) break;
-    __syncthreads();
-    if (lane < K) mstep_state(r, p.h, lane);
-    __syncthreads();
-    if (flags & 1) break;
-  }
+  const size_t PL = post_len(KM, dim), SL = stats_len(KM, dim);
+  const int iters = run_em<KM>(WaveLanes{lane}, r, K, dim, s, p.h, p.max_iter, p.min_diff, p.post + run * PL,
+                               gamma_only ? nullptr : p.post_out + run * PL,
+                               p.post_estep ? p.post_estep + run * PL : nullptr,
+                               p.stats ? p.stats + run * SL : nullptr,
+                               p.LLs ? p.LLs + (size_t)run * p.max_iter : nullptr, w, gamma_only);
+  if (lane != 0) return;
   if (gamma_only) {
-    if (lane == 0 && p.status) p.status[run] = kConverged;
+    if (p.status) p.status[run] = kConverged;
     return;
   }
-  for (int x = lane; x < PL; x += 64) p.post_out[(size_t)run * PL + x] = r.post[x];
-  if (lane == 0) {
-    p.LL[run] = r.L;
-    p.iters[run] = it > p.max_iter ? p.max_iter : it;
-    p.status[run] = status_of(r.flags);
-  }
+  p.LL[run] = r.L;
+  p.iters[run] = iters;
+  p.status[run] = status_of(r.flags);
 }
 
 size_t slot_doubles(int KM, int max_seqs, int max_obs) {
   return (size_t)std::max(max_obs, 1) * obs_len(KM) + (size_t)std::max(max_seqs, 1) * seq_len(KM);
 }
 
-// Runs per launch: the caller's, or the default -- VBHMM_EM_DEFAULT_CHUNK runs (a launch of
-// that many runs at 25 sequences x 50 observations takes 0.13 s), fewer
-// where their workspace would pass VBHMM_EM_DEFAULT_WORKSPACE bytes.
-int chunk_of(int chunk_runs, size_t slot) {
-  if (chunk_runs > 0) return chunk_runs;
-  const size_t fit = (size_t)VBHMM_EM_DEFAULT_WORKSPACE / (slot * sizeof(double));
-  return (int)std::max<size_t>(1, std::min<size_t>(VBHMM_EM_DEFAULT_CHUNK, fit));
-}
-
 int check_sizes(const vbhmm_em_subjects_t *sb, int R, int KM) {
-  if (!sb) return set_error(VBHEM_ERR_ARG, "vbhmm_em: null subjects");
-  if (sb->S < 1 || sb->seqs.N < 0 || sb->seqs.dim < 1 || sb->max_seqs < 0 || sb->max_obs < 0 || R < 0 || KM < 1)
-    return set_error(VBHEM_ERR_ARG, "vbhmm_em: need S >= 1, dim >= 1, KM >= 1 and non-negative counts");
-  if (sb->seqs.dim > kMaxDim || KM > kMaxStates)
-    return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_em: K <= 8 and dim <= 8 supported");
-  if (KM != 4 && KM != 8) return set_error(VBHEM_ERR_ARG, "vbhmm_em: KM is 4 or 8");
-  return VBHEM_OK;
+  return batch::check_sizes("vbhmm_em", sb, sb ? sb->max_seqs : 0, R, KM);
 }
 
 int launch_chunks(EmArgs &a, int R, int KM, int chunk_runs, void *workspace_dev, size_t workspace_bytes,
                   hipStream_t st) {
   a.slot = slot_doubles(KM, a.max_seqs, a.max_obs);
-  const int chunk = chunk_of(chunk_runs, a.slot);
-  const size_t need = (size_t)std::min(R, chunk) * a.slot * sizeof(double);
-  if (!workspace_dev || workspace_bytes < need)
-    return set_error(VBHEM_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  a.ws = static_cast<double *>(workspace_dev);
-  for (int r0 = 0; r0 < R; r0 += chunk) {
-    a.R0 = r0;
-    const unsigned n = (unsigned)std::min(chunk, R - r0);
-    if (KM == 4)
-      hipLaunchKernelGGL(vbhmm_em_kernel<4>, dim3(n), dim3(64), 0, st, a);
-    else
-      hipLaunchKernelGGL(vbhmm_em_kernel<8>, dim3(n), dim3(64), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vbhmm_em_kernel");
-  }
-  return VBHEM_OK;
+  return batch::launch_chunks(a, R, KM, chunk_runs, workspace_dev, workspace_bytes, st, vbhmm_em_kernel<4>,
+                              vbhmm_em_kernel<8>, "vbhmm_em_kernel");
 }
 
 void fill_common(EmArgs &a, const vbhmm_em_subjects_t *sb, const vbhmm_em_runs_t *runs) {
@@ -214,8 +142,7 @@ size_t vbhmm_em_stats_len(int KM, int dim) { return (size_t)vbhem::emrun::stats_
 size_t vbhmm_em_batch_workspace_bytes(const vbhmm_em_subjects_t *sb, int R, int KM, int chunk_runs) {
   using namespace vbhem;
   if (check_sizes(sb, R, KM) != VBHEM_OK) return 0;
-  const size_t slot = slot_doubles(KM, sb->max_seqs, sb->max_obs);
-  return std::max<size_t>(256, (size_t)std::min(R, chunk_of(chunk_runs, slot)) * slot * sizeof(double));
+  return batch::workspace_bytes(R, chunk_runs, slot_doubles(KM, sb->max_seqs, sb->max_obs));
 }
 
 int vbhmm_em_batch(const vbhmm_em_subjects_t *sb, const vbhmm_em_runs_t *runs, const vbhmm_em_hyper_t *hyper,
@@ -235,11 +162,7 @@ int vbhmm_em_batch(const vbhmm_em_subjects_t *sb, const vbhmm_em_runs_t *runs, c
   fill_common(a, sb, runs);
   a.max_iter = opt->max_iter;
   a.min_diff = opt->min_diff;
-  a.h.alpha0 = hyper->alpha0; a.h.epsilon0 = hyper->epsilon0; a.h.beta0 = hyper->beta0; a.h.v0 = hyper->v0;
-  for (int q = 0; q < emrun::kMaxDim; ++q) {
-    a.h.m0[q] = q < a.dim ? hyper->m0[q] : 0.0;
-    a.h.W0inv[q] = q < a.dim ? hyper->W0inv_diag[q] : 1.0;
-  }
+  a.h = batch::to_hyper(hyper, a.dim);
   a.post_out = post_out_dev; a.post_estep = post_estep_dev; a.stats = stats_dev;
   a.LL = LL_dev; a.iters = iters_dev; a.status = status_dev; a.LLs = LLs_dev;
   return launch_chunks(a, runs->R, runs->KM, opt->chunk_runs, workspace_dev, workspace_bytes,

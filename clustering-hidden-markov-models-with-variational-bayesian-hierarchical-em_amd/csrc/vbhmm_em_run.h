@@ -14,9 +14,11 @@
 //   M-step    vbhmm_em.m:352-383; W_k by a Cholesky-based inverse in place
 //
 // The units are one STATE (prelude_state, bound_state, mstep_state), one SEQUENCE
-// (fb_sequence) and one statistic ENTRY (stat_*).  The device kernel gives a unit to a
-// lane; run_serial below walks the units in loops and is what the host build checks
-// against the oracle.  Both read and write the same Run<KM> (LDS on the device).
+// (fb_sequence) and one statistic ENTRY (stat_*).  Which units run in which order, when
+// the loop ends and what is captured when is run_em below, written once: the device
+// kernel walks it with a unit per lane (WaveLanes), run_serial with plain loops
+// (SerialLanes), which is what the host build checks against the oracle.  Both read and
+// write the same Run<KM> (LDS on the device).
 //
 // Padding: a run has K <= KM own states; every loop runs over K, padding is never read
 // into a sum, so a run's result does not depend on KM.  A NaN (log det of an indefinite
@@ -25,12 +27,11 @@
 #pragma once
 #include <cmath>
 
+#include "vbhem_special.h"  // VBE_HD, psi_onediv, lgamma_stirling
+
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define VBE_HD __host__ __device__
 #define VBE_UNROLL _Pragma("unroll")
 #else
-#define VBE_HD
 #define VBE_UNROLL
 #endif
 
@@ -64,38 +65,6 @@ struct Hyper {
   double m0[kMaxDim];
   double W0inv[kMaxDim];  // the diagonal of W0^-1
 };
-
-// digamma for x > 0: psi(x) = psi(x + n) - sum_{i<n} 1/(x + i) with x + n >= 8, then the
-// asymptotic series (the series of vbhem_em_dev.hip's psi_dev)
-VBE_HD inline double psi(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : __builtin_nan("");
-  double num = 0.0, den = 1.0;
-  while (x < 8.0) {
-    num = fma(num, x, den);
-    den *= x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 -
-      r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
-  return log(x) - 0.5 * r - series - num / den;
-}
-
-// log Gamma for x > 0: Stirling's series at z = x + n >= 10 (vbhem_em_dev.hip's lgamma_dev)
-VBE_HD inline double lgam(double x) {
-  if (!(x > 0.0 && x < INFINITY)) return x == INFINITY ? x : __builtin_nan("");
-  double prod = 1.0;
-  while (x < 10.0) {
-    prod *= x;
-    x += 1.0;
-  }
-  const double r = 1.0 / x, r2 = r * r;
-  const double series =
-      r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 -
-      r2 * (691.0 / 360360 - r2 * (1.0 / 156 - r2 * (3617.0 / 122400))))))));
-  return (x - 0.5) * log(x) - x + 0.91893853320467274178 + series - log(prod);
-}
 
 // per-state terms of the bound, summed over the states in state order by bound_total
 enum { qLt1, qMlA, qSumlA, qLt51, qlLT, qvTrW0W, qAlPi, qLgAlpha, qLt72, qLt8a, qH, qlPi, kNQ };
@@ -198,7 +167,7 @@ VBE_HD inline void prelude_state(Run<KM> &r, int k) {
   const int K = r.K, dim = r.dim;
   const double v = r.v()[k];
   double t1 = 0.0;
-  for (int q = 1; q <= dim; ++q) t1 += psi(0.5 * (v + 1.0) - 0.5 * q);
+  for (int q = 1; q <= dim; ++q) t1 += psi_onediv(0.5 * (v + 1.0) - 0.5 * q);
   double *sc = r.S() + k * dim * dim;
   const double *W = r.W() + k * dim * dim;
   for (int x = 0; x < dim * dim; ++x) sc[x] = W[x];
@@ -211,13 +180,13 @@ VBE_HD inline void prelude_state(Run<KM> &r, int k) {
     se += r.eps()[k * KM + j];
     sa += r.alpha()[j];
   }
-  const double pse = psi(se);
+  const double pse = psi_onediv(se);
   for (int j = 0; j < K; ++j) {
-    const double la = psi(r.eps()[k * KM + j]) - pse;
+    const double la = psi_onediv(r.eps()[k * KM + j]) - pse;
     r.logA[k * KM + j] = la;
     r.A[k * KM + j] = exp(la);
   }
-  const double lp = psi(r.alpha()[k]) - psi(sa);
+  const double lp = psi_onediv(r.alpha()[k]) - psi_onediv(sa);
   r.logPi[k] = lp;
   r.pz1[k] = exp(lp);
 }
@@ -380,7 +349,7 @@ VBE_HD inline void bound_state(Run<KM> &r, const Hyper &h, int k) {
   const double *W = r.W() + k * dim * dim, *m = r.m() + k * dim, *S = r.S() + k * dim * dim;
   const double *xb = r.xbar() + k * dim;
   double sg = 0.0;
-  for (int q = 1; q <= dim; ++q) sg += lgam(0.5 * (v + 1 - q));
+  for (int q = 1; q <= dim; ++q) sg += lgamma_stirling(0.5 * (v + 1 - q));
   const double logBk = -(v / 2) * r.logdetW[k] - (v * dim / 2) * kLn2 - (dim * (dim - 1) / 4.0) * kLnPi - sg;
   double trSW = 0.0, xWx = 0.0, mWm = 0.0, trW0W = 0.0;
   for (int a = 0; a < dim; ++a) {
@@ -398,7 +367,7 @@ VBE_HD inline void bound_state(Run<KM> &r, const Hyper &h, int k) {
   for (int j = 0; j < K; ++j) {
     const double e = r.eps()[k * KM + j], la = r.logA[k * KM + j];
     se += e;
-    sle += lgam(e);
+    sle += lgamma_stirling(e);
     MlA += r.M()[k * KM + j] * la;
     slA += la;
     elA += (e - 1) * la;
@@ -411,8 +380,8 @@ VBE_HD inline void bound_state(Run<KM> &r, const Hyper &h, int k) {
   q[qlLT] = lLT;
   q[qvTrW0W] = v * trW0W;
   q[qAlPi] = (r.alpha()[k] - 1) * lPi;
-  q[qLgAlpha] = lgam(r.alpha()[k]);
-  q[qLt72] = elA + (lgam(se) - sle);
+  q[qLgAlpha] = lgamma_stirling(r.alpha()[k]);
+  q[qLt72] = elA + (lgamma_stirling(se) - sle);
   q[qLt8a] = lLT + dim * log(beta / (2 * kPi));
   q[qH] = -logBk - 0.5 * (v - dim - 1) * lLT + 0.5 * v * dim;
   q[qlPi] = lPi;
@@ -439,12 +408,12 @@ VBE_HD inline double bound_total(const Run<KM> &r, const Hyper &h, int N, const 
   double logdetW0inv = 0.0, sg0 = 0.0;
   for (int a = 0; a < dim; ++a) {
     logdetW0inv += log(h.W0inv[a]);
-    sg0 += lgam(0.5 * (h.v0 - a));
+    sg0 += lgamma_stirling(0.5 * (h.v0 - a));
   }
-  const double logCalpha0 = lgam(K * h.alpha0) - K * lgam(h.alpha0);
-  const double logCeps0 = lgam(K * h.epsilon0) - K * lgam(h.epsilon0);
+  const double logCalpha0 = lgamma_stirling(K * h.alpha0) - K * lgamma_stirling(h.alpha0);
+  const double logCeps0 = lgamma_stirling(K * h.epsilon0) - K * lgamma_stirling(h.epsilon0);
   const double logB0 = (h.v0 / 2) * logdetW0inv - (h.v0 * dim / 2) * kLn2 - (dim * (dim - 1) / 4.0) * kLnPi - sg0;
-  const double logCalpha = lgam(sa) - t[qLgAlpha];
+  const double logCalpha = lgamma_stirling(sa) - t[qLgAlpha];
   const double Lt1 = 0.5 * t[qLt1];
   const double Lt2b = t[qMlA];
   const double Lt2 = Lt2a + Lt2b;
@@ -505,58 +474,115 @@ struct RunResult {
   int iters, status;
 };
 
+// ---- who walks the units of a phase.  once(count, f): f(u) for every u < count, where
+// count cannot pass the wave's 64 lanes; each(count, f): the same for any count; sync():
+// between two phases, what one wrote the next may read; first(): true for the one walker
+// that takes the run's scalar decisions.  Units of a phase are independent, so the order
+// in which a policy visits them changes no bit.
+struct SerialLanes {
+  template <class F>
+  VBE_HD void once(int count, F f) const {
+    for (int u = 0; u < count; ++u) f(u);
+  }
+  template <class F>
+  VBE_HD void each(int count, F f) const {
+    for (int u = 0; u < count; ++u) f(u);
+  }
+  VBE_HD void sync() const {}
+  VBE_HD bool first() const { return true; }
+};
+
+#if defined(__HIPCC__)
+// A workgroup of ONE wavefront: a unit per lane.  The barrier is a memory fence and
+// nothing to wait for.
+struct WaveLanes {
+  int lane;
+  template <class F>
+  __device__ __forceinline__ void once(int count, F f) const {
+    if (lane < count) f(lane);
+  }
+  template <class F>
+  __device__ __forceinline__ void each(int count, F f) const {
+    for (int u = lane; u < count; u += 64) f(u);
+  }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  __device__ __forceinline__ bool first() const { return lane == 0; }
+};
+#endif
+
+// ---- the schedule of one whole run: the device kernel walks it with WaveLanes, run_serial
+// with SerialLanes.  r: the run's state (LDS on the device), filled here; post_in
+// [post_len]: the initial posterior; post_out: the posterior after the last M-step (may be
+// post_in); post_estep / stats (or null): the posterior at the last E-step and its
+// statistics; LLs (or null): [max_iter], entries past the iteration count untouched.  w is
+// sized for the subject; on return w.gamma holds the last E-step's gamma.  gamma_only:
+// prelude + phase A once, nothing but w.gamma written.  Returns the iteration count; the
+// bound and the status are r.L and status_of(r.flags).
+template <int KM, class Lanes>
+VBE_HD inline int run_em(const Lanes lanes, Run<KM> &r, int K, int dim, const Subject &s, const Hyper &h,
+                         int max_iter, double min_diff, const double *post_in, double *post_out,
+                         double *post_estep, double *stats, double *LLs, const Work<KM> &w, bool gamma_only) {
+  const int PL = post_len(KM, dim), SL = stats_len(KM, dim), N = s.N, base = s.off[0];
+  lanes.each(PL, [&](int x) { r.post[x] = post_in[x]; });
+  lanes.each(SL, [&](int x) { r.stats[x] = 0.0; });
+  if (lanes.first()) {
+    r.K = K;
+    r.dim = dim;
+    r.L = r.lastL = -1.7976931348623157e308;
+    r.flags = 0;
+  }
+  lanes.sync();
+  int it = 1;
+  for (; it <= max_iter; ++it) {
+    lanes.once(K, [&](int k) { prelude_state(r, k); });
+    lanes.sync();
+    lanes.each(N, [&](int n) {
+      const int q = s.off[n] - base, T = s.off[n + 1] - s.off[n];
+      fb_sequence<KM>(r, s.x + (size_t)s.off[n] * dim, T, w.gamma + (size_t)q * KM, w.logrho + (size_t)q * KM,
+                      w.cs + q, w.mxs + q, w.seq + (size_t)n * seq_len(KM));
+    });
+    if (gamma_only) return it;
+    lanes.sync();
+    lanes.once(K, [&](int k) { stat_counts(r, s, w, k); });
+    lanes.once(KM * KM, [&](int e) {
+      if (e / KM < K && e % KM < K) stat_trans(r, s, w, e / KM, e % KM);
+    });
+    lanes.sync();
+    lanes.once(K * dim, [&](int e) { stat_mean(r, s, w, e / dim, e % dim); });
+    lanes.sync();
+    lanes.each(K * dim * dim, [&](int e) { stat_cov(r, s, w, e / (dim * dim), (e / dim) % dim, e % dim); });
+    lanes.sync();
+    lanes.once(K, [&](int k) { bound_state(r, h, k); });
+    lanes.sync();
+    if (lanes.first()) {
+      loop_control(r, bound_total(r, h, N, w.seq), it, max_iter, min_diff);
+      if (LLs) LLs[it - 1] = r.L;
+    }
+    lanes.sync();
+    const int flags = r.flags;
+    if (flags & 1) {  // the last E-step: its posterior and statistics
+      if (post_estep) lanes.each(PL, [&](int x) { post_estep[x] = r.post[x]; });
+      if (stats) lanes.each(SL, [&](int x) { stats[x] = r.stats[x]; });
+    }
+    if (flags & 4) break;
+    lanes.sync();
+    lanes.once(K, [&](int k) { mstep_state(r, h, k); });
+    lanes.sync();
+    if (flags & 1) break;
+  }
+  lanes.each(PL, [&](int x) { post_out[x] = r.post[x]; });
+  return it > max_iter ? max_iter : it;
+}
+
 // ---- one whole run, unit after unit (host builds only).  post [post_len]: the initial
-// posterior in, the posterior after the last M-step out; post_estep / stats (or null): the
-// posterior at the last E-step and its statistics; LLs (or null): [max_iter], entries past
-// iters untouched.  The caller provides the workspace arrays of Work<KM>, sized for the
-// subject; on return w.gamma holds the last E-step's gamma.
+// posterior in, the posterior after the last M-step out; the rest as run_em's.
 template <int KM>
 inline RunResult run_serial(int K, int dim, const Subject &s, const Hyper &h, int max_iter, double min_diff,
                             double *post, double *post_estep, double *stats, double *LLs, const Work<KM> &w) {
   Run<KM> r;
-  r.K = K;
-  r.dim = dim;
-  const int PL = post_len(KM, dim), SL = stats_len(KM, dim);
-  for (int x = 0; x < PL; ++x) r.post[x] = post[x];
-  for (int x = 0; x < SL; ++x) r.stats[x] = 0.0;
-  r.L = r.lastL = -1.7976931348623157e308;
-  r.flags = 0;
-  const int base = s.off[0];
-  int it = 0;
-  for (it = 1; it <= max_iter; ++it) {
-    for (int k = 0; k < K; ++k) prelude_state(r, k);
-    for (int n = 0; n < s.N; ++n) {
-      const int p = s.off[n] - base, T = s.off[n + 1] - s.off[n];
-      fb_sequence<KM>(r, s.x + (size_t)s.off[n] * dim, T, w.gamma + (size_t)p * KM, w.logrho + (size_t)p * KM,
-                      w.cs + p, w.mxs + p, w.seq + (size_t)n * seq_len(KM));
-    }
-    for (int k = 0; k < K; ++k) stat_counts(r, s, w, k);
-    for (int i = 0; i < K; ++i)
-      for (int j = 0; j < K; ++j) stat_trans(r, s, w, i, j);
-    for (int k = 0; k < K; ++k)
-      for (int a = 0; a < dim; ++a) stat_mean(r, s, w, k, a);
-    for (int k = 0; k < K; ++k)
-      for (int a = 0; a < dim; ++a)
-        for (int b = 0; b < dim; ++b) stat_cov(r, s, w, k, a, b);
-    for (int k = 0; k < K; ++k) bound_state(r, h, k);
-    loop_control(r, bound_total(r, h, s.N, w.seq), it, max_iter, min_diff);
-    if (LLs) LLs[it - 1] = r.L;
-    if (r.flags & 1) {
-      if (post_estep)
-        for (int x = 0; x < PL; ++x) post_estep[x] = r.post[x];
-      if (stats)
-        for (int x = 0; x < SL; ++x) stats[x] = r.stats[x];
-    }
-    if (r.flags & 4) break;
-    for (int k = 0; k < K; ++k) mstep_state(r, h, k);
-    if (r.flags & 1) break;
-  }
-  for (int x = 0; x < PL; ++x) post[x] = r.post[x];
-  RunResult out;
-  out.LL = r.L;
-  out.iters = it > max_iter ? max_iter : it;
-  out.status = status_of(r.flags);
-  return out;
+  const int iters =
+      run_em<KM>(SerialLanes{}, r, K, dim, s, h, max_iter, min_diff, post, post, post_estep, stats, LLs, w, false);
+  return RunResult{r.L, iters, status_of(r.flags)};
 }
 
 }  // namespace emrun

@@ -1,12 +1,14 @@
 // vbhmm_gmm.hip -- the batched random-start GMM fit (include/vbhmm_gmm.h): every fit of a
 // list, from its start rows to its last M-step, in one call; optionally the initial VB-HMM
-// posterior of each fitted GMM.  The arithmetic of a fit is vbhmm_gmm_run.h, shared with
-// the host check build.
+// posterior of each fitted GMM.  The arithmetic of a fit AND its schedule (run_fit) are
+// vbhmm_gmm_run.h, shared with the host check build; the kernel's own are the check of the
+// fit against the workspace sizes, the carving of the slot and the fit's ll / iters / status.
 //
 // vbhmm_gmm_kernel<KM>: a workgroup is ONE wavefront and owns ONE fit (fit = chunk start +
 // blockIdx.x) for its whole EM; the fit's small state (pi, mu, cov, the factors L and their
 // log-determinants: Fit<KM>) lives in the workgroup's LDS, the responsibilities [N][KM] and
-// the row log-sum-exps [N] in the workspace slot of the workgroup.  Per iteration:
+// the row log-sum-exps [N] in the workspace slot of the workgroup.  run_fit with a unit per
+// lane (emrun::WaveLanes) is, per iteration:
 //   factor    a lane per state; a failed pivot ends the fit (wave-uniform: every lane reads
 //             the states' flags after the barrier)
 //   E-step    a lane per observation, in rounds of 64 (estep_obs)
@@ -27,6 +29,7 @@
 
 #include "vbhem_estep.h"
 #include "vbhem_internal.h"
+#include "vbhmm_batch_launch.h"
 #include "vbhmm_gmm.h"
 #include "vbhmm_gmm_run.h"
 
@@ -47,8 +50,10 @@ struct GmmArgs {
   size_t slot;  // doubles per workgroup
 };
 
+// <4> runs at 3 waves per SIMD and sits a few registers under the step to 2: its bound
+// says so.
 template <int KM>
-__global__ __launch_bounds__(64, KM == 4 ? 2 : 1) void vbhmm_gmm_kernel(const GmmArgs p) {
+__global__ __launch_bounds__(64, KM == 4 ? 3 : 1) void vbhmm_gmm_kernel(const GmmArgs p) {
   __shared__ Fit<KM> f;
   const int lane = threadIdx.x;
   const int fit = p.R0 + blockIdx.x;
@@ -76,82 +81,22 @@ __global__ __launch_bounds__(64, KM == 4 ? 2 : 1) void vbhmm_gmm_kernel(const Gm
   double *slot = p.ws + (size_t)blockIdx.x * p.slot;
   const Work w{slot, slot + (size_t)p.max_obs * KM};
 
+  const FitResult res = run_fit<KM>(
+      emrun::WaveLanes{lane}, f, K, dim, N, x, rows, p.reg[fit], p.max_iter, p.tolfun, p.prior + (size_t)fit * KM,
+      p.mean + (size_t)fit * KM * dim, p.cov + (size_t)fit * KM * dim * dim,
+      p.lls ? p.lls + (size_t)fit * p.max_iter : nullptr, &p.h,
+      p.post_init ? p.post_init + (size_t)fit * emrun::post_len(KM, dim) : nullptr, w);
   if (lane == 0) {
-    f.K = K;
-    f.dim = dim;
-    f.N = N;
-    f.reg = p.reg[fit];
-    f.ll = __builtin_nan("");
-    f.last = -INFINITY;
-    f.flags = 0;
-  }
-  __syncthreads();
-  if (lane < dim) start_var(f, x, lane);
-  if (lane < K * dim) start_mean(f, x, rows, lane / dim, lane % dim);
-  __syncthreads();
-  for (int e = lane; e < K * dim * dim; e += 64) start_cov(f, e / (dim * dim), (e / dim) % dim, e % dim);
-  __syncthreads();
-
-  int it = 1;
-  bool ill = false;
-  for (; it <= p.max_iter; ++it) {
-    if (lane < K) factor_state(f, lane);
-    __syncthreads();
-    if (any_bad(f)) {
-      ill = true;
-      break;
-    }
-    for (int n = lane; n < N; n += 64) estep_obs<KM>(f, x + (size_t)n * dim, w.post + (size_t)n * KM, w.lse + n);
-    __syncthreads();
-    if (lane < K) stat_nk(f, w, lane);
-    else if (lane == K) stat_ll(f, w);
-    __syncthreads();
-    if (lane < K * dim) stat_mean(f, x, w, lane / dim, lane % dim);
-    __syncthreads();
-    for (int e = lane; e < K * dim * dim; e += 64) stat_cov(f, x, w, e / (dim * dim), (e / dim) % dim, e % dim);
-    if (lane == 0) {
-      loop_control(f, it, p.max_iter, p.tolfun);
-      if (p.lls) p.lls[(size_t)fit * p.max_iter + (it - 1)] = f.ll;
-    }
-    __syncthreads();
-    if (f.flags & 1) break;
-  }
-  if (lane == 0) {
-    p.ll[fit] = f.ll;
-    p.iters[fit] = it > p.max_iter ? p.max_iter : it;
-    p.status[fit] = ill ? kIllConditioned : status_of(f.flags);
-  }
-  if (ill) return;
-  if (lane < K) p.prior[(size_t)fit * KM + lane] = f.pi[lane];
-  if (lane < K * dim) p.mean[(size_t)fit * KM * dim + lane] = f.mu[lane];
-  for (int e = lane; e < K * dim * dim; e += 64) p.cov[(size_t)fit * KM * dim * dim + e] = f.cov[e];
-  if (p.post_init) {
-    const int PL = emrun::post_len(KM, dim);
-    double *post = p.post_init + (size_t)fit * PL;
-    for (int q = lane; q < PL; q += 64) post[q] = post_padding(KM, dim, q);
-    __syncthreads();
-    if (lane < K) init_posterior_state(f, p.h, lane, post);
+    p.ll[fit] = res.ll;
+    p.iters[fit] = res.iters;
+    p.status[fit] = res.status;
   }
 }
 
 size_t slot_doubles(int KM, int max_obs) { return (size_t)std::max(max_obs, 1) * obs_len(KM); }
 
-// Fits per launch: the caller's, or the default -- VBHMM_EM_DEFAULT_CHUNK fits, fewer where
-// their workspace would pass VBHMM_EM_DEFAULT_WORKSPACE bytes.
-int chunk_of(int chunk_runs, size_t slot) {
-  if (chunk_runs > 0) return chunk_runs;
-  const size_t fit = (size_t)VBHMM_EM_DEFAULT_WORKSPACE / (slot * sizeof(double));
-  return (int)std::max<size_t>(1, std::min<size_t>(VBHMM_EM_DEFAULT_CHUNK, fit));
-}
-
 int check_sizes(const vbhmm_em_subjects_t *sb, int R, int KM) {
-  if (!sb) return set_error(VBHEM_ERR_ARG, "vbhmm_gmm: null subjects");
-  if (sb->S < 1 || sb->seqs.N < 0 || sb->seqs.dim < 1 || sb->max_obs < 0 || R < 0 || KM < 1)
-    return set_error(VBHEM_ERR_ARG, "vbhmm_gmm: need S >= 1, dim >= 1, KM >= 1 and non-negative counts");
-  if (sb->seqs.dim > kMaxDim || KM > kMaxStates)
-    return set_error(VBHEM_ERR_UNSUPPORTED, "vbhmm_gmm: K <= 8 and dim <= 8 supported");
-  if (KM != 4 && KM != 8) return set_error(VBHEM_ERR_ARG, "vbhmm_gmm: KM is 4 or 8");
-  return VBHEM_OK;
+  return batch::check_sizes("vbhmm_gmm", sb, 0, R, KM);
 }
 
 }  // namespace
@@ -162,8 +107,7 @@ extern "C" {
 size_t vbhmm_gmm_fit_workspace_bytes(const vbhmm_em_subjects_t *sb, int R, int KM, int chunk_runs) {
   using namespace vbhem;
   if (check_sizes(sb, R, KM) != VBHEM_OK) return 0;
-  const size_t slot = slot_doubles(KM, sb->max_obs);
-  return std::max<size_t>(256, (size_t)std::min(R, chunk_of(chunk_runs, slot)) * slot * sizeof(double));
+  return batch::workspace_bytes(R, chunk_runs, slot_doubles(KM, sb->max_obs));
 }
 
 int vbhmm_gmm_fit_batch(const vbhmm_em_subjects_t *sb, const vbhmm_gmm_fits_t *fits, const vbhmm_gmm_opt_t *opt,
@@ -190,32 +134,11 @@ int vbhmm_gmm_fit_batch(const vbhmm_em_subjects_t *sb, const vbhmm_gmm_fits_t *f
   a.tolfun = opt->tolfun;
   a.prior = prior_dev; a.mean = mean_dev; a.cov = cov_dev; a.ll = ll_dev; a.lls = lls_dev;
   a.iters = iters_dev; a.status = status_dev; a.post_init = post_init_dev;
-  if (hyper) {
-    a.h.alpha0 = hyper->alpha0; a.h.epsilon0 = hyper->epsilon0; a.h.beta0 = hyper->beta0; a.h.v0 = hyper->v0;
-    for (int q = 0; q < kMaxDim; ++q) {
-      a.h.m0[q] = q < a.dim ? hyper->m0[q] : 0.0;
-      a.h.W0inv[q] = q < a.dim ? hyper->W0inv_diag[q] : 1.0;
-    }
-  }
-  const int R = fits->R, KM = fits->KM;
-  a.slot = slot_doubles(KM, a.max_obs);
-  const int chunk = chunk_of(opt->chunk_runs, a.slot);
-  const size_t need = (size_t)std::min(R, chunk) * a.slot * sizeof(double);
-  if (!workspace_dev || workspace_bytes < need)
-    return set_error(VBHEM_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  a.ws = static_cast<double *>(workspace_dev);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  for (int r0 = 0; r0 < R; r0 += chunk) {
-    a.R0 = r0;
-    const unsigned n = (unsigned)std::min(chunk, R - r0);
-    if (KM == 4)
-      hipLaunchKernelGGL(vbhmm_gmm_kernel<4>, dim3(n), dim3(64), 0, st, a);
-    else
-      hipLaunchKernelGGL(vbhmm_gmm_kernel<8>, dim3(n), dim3(64), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vbhmm_gmm_kernel");
-  }
-  return VBHEM_OK;
+  if (hyper) a.h = batch::to_hyper(hyper, a.dim);
+  a.slot = slot_doubles(fits->KM, a.max_obs);
+  return batch::launch_chunks(a, fits->R, fits->KM, opt->chunk_runs, workspace_dev, workspace_bytes,
+                              static_cast<hipStream_t>(stream), vbhmm_gmm_kernel<4>, vbhmm_gmm_kernel<8>,
+                              "vbhmm_gmm_kernel");
 }
 
 }  // extern "C"

@@ -16,9 +16,11 @@
 // layout of include/vbhmm_em.h, its W by the Cholesky-based inverse of vbhmm_em_run.h.
 //
 // The units are one STATE (factor_state, init_posterior_state), one OBSERVATION
-// (estep_obs) and one statistic ENTRY (start_var, stat_*).  The device kernel gives a
-// unit to a lane; run_serial below walks the units in loops.  Both read and write the
-// same Fit<KM> (LDS on the device).
+// (estep_obs) and one statistic ENTRY (start_var, stat_*).  Which units run in which
+// order, when the loop ends and what an ill-conditioned fit leaves unwritten is run_fit
+// below, written once: the device kernel walks it with a unit per lane, run_serial with
+// plain loops (the lane policies of vbhmm_em_run.h).  Both read and write the same
+// Fit<KM> (LDS on the device).
 //
 // Padding: a fit has K <= KM own states; every loop runs over K, so a fit's result does
 // not depend on KM.  log(0) = -inf proportions, zero covariances and NaN flow through to
@@ -278,69 +280,83 @@ struct FitResult {
   int iters, status;
 };
 
-// ---- one whole fit, unit after unit (host builds only).  x: the subject's first row, N
-// rows.  prior [KM], mean [KM][dim], cov [KM][dim][dim]: rows k < K written, and only for
-// a fit that ends converged or at max_iter; lls (or null): [max_iter], entries past iters
-// untouched; h / post_init (or null): the packed initial posterior, written under the same
-// condition.  A fit that is not valid returns kBadFit and writes nothing.
-template <int KM>
-inline FitResult run_serial(int K, int dim, int N, int max_obs, const double *x, const int *rows, double reg,
-                            int max_iter, double tolfun, double *prior, double *mean, double *cov, double *lls,
-                            const Hyper *h, double *post_init, const Work &w) {
-  FitResult out{__builtin_nan(""), 0, kBadFit};
-  if (!fit_valid(K, KM, N, max_obs, rows)) return out;
-  Fit<KM> f;
-  f.K = K;
-  f.dim = dim;
-  f.N = N;
-  f.reg = reg;
-  f.ll = __builtin_nan("");
-  f.last = -INFINITY;
-  f.flags = 0;
-  for (int a = 0; a < dim; ++a) start_var(f, x, a);
-  for (int k = 0; k < K; ++k)
-    for (int a = 0; a < dim; ++a) start_mean(f, x, rows, k, a);
-  for (int k = 0; k < K; ++k)
-    for (int a = 0; a < dim; ++a)
-      for (int b = 0; b < dim; ++b) start_cov(f, k, a, b);
+// ---- the schedule of one whole fit (emrun's lane policies): the device kernel walks it
+// with WaveLanes, run_serial with SerialLanes.  f: the fit's state (LDS on the device),
+// filled here; the fit is valid (fit_valid).  x: the subject's first row, N rows.  The
+// outputs are this fit's own: prior [KM], mean [KM][dim], cov [KM][dim][dim], rows k < K
+// written, and only for a fit that ends converged or at max_iter; lls (or null):
+// [max_iter], entries past iters untouched; h / post_init (or null): the packed initial
+// posterior, written under the same condition.
+template <int KM, class Lanes>
+VBE_HD inline FitResult run_fit(const Lanes lanes, Fit<KM> &f, int K, int dim, int N, const double *x,
+                                const int *rows, double reg, int max_iter, double tolfun, double *prior,
+                                double *mean, double *cov, double *lls, const Hyper *h, double *post_init,
+                                const Work &w) {
+  if (lanes.first()) {
+    f.K = K;
+    f.dim = dim;
+    f.N = N;
+    f.reg = reg;
+    f.ll = __builtin_nan("");
+    f.last = -INFINITY;
+    f.flags = 0;
+  }
+  lanes.sync();
+  lanes.once(dim, [&](int a) { start_var(f, x, a); });
+  lanes.once(K * dim, [&](int e) { start_mean(f, x, rows, e / dim, e % dim); });
+  lanes.sync();
+  lanes.each(K * dim * dim, [&](int e) { start_cov(f, e / (dim * dim), (e / dim) % dim, e % dim); });
+  lanes.sync();
   int it = 1;
   bool ill = false;
   for (; it <= max_iter; ++it) {
-    for (int k = 0; k < K; ++k) factor_state(f, k);
+    lanes.once(K, [&](int k) { factor_state(f, k); });
+    lanes.sync();
     if (any_bad(f)) {
       ill = true;
       break;
     }
-    for (int n = 0; n < N; ++n) estep_obs<KM>(f, x + (size_t)n * dim, w.post + (size_t)n * KM, w.lse + n);
-    stat_ll(f, w);
-    for (int k = 0; k < K; ++k) stat_nk(f, w, k);
-    for (int k = 0; k < K; ++k)
-      for (int a = 0; a < dim; ++a) stat_mean(f, x, w, k, a);
-    for (int k = 0; k < K; ++k)
-      for (int a = 0; a < dim; ++a)
-        for (int b = 0; b < dim; ++b) stat_cov(f, x, w, k, a, b);
-    loop_control(f, it, max_iter, tolfun);
-    if (lls) lls[it - 1] = f.ll;
+    lanes.each(N, [&](int n) { estep_obs<KM>(f, x + (size_t)n * dim, w.post + (size_t)n * KM, w.lse + n); });
+    lanes.sync();
+    lanes.once(K + 1, [&](int k) {
+      if (k < K) stat_nk(f, w, k);
+      else stat_ll(f, w);
+    });
+    lanes.sync();
+    lanes.once(K * dim, [&](int e) { stat_mean(f, x, w, e / dim, e % dim); });
+    lanes.sync();
+    lanes.each(K * dim * dim, [&](int e) { stat_cov(f, x, w, e / (dim * dim), (e / dim) % dim, e % dim); });
+    if (lanes.first()) {
+      loop_control(f, it, max_iter, tolfun);
+      if (lls) lls[it - 1] = f.ll;
+    }
+    lanes.sync();
     if (f.flags & 1) break;
   }
-  out.ll = f.ll;
-  out.iters = it > max_iter ? max_iter : it;
-  if (ill) {
-    out.status = kIllConditioned;
-    return out;
+  if (!ill) {
+    lanes.once(K, [&](int k) { prior[k] = f.pi[k]; });
+    lanes.once(K * dim, [&](int e) { mean[e] = f.mu[e]; });
+    lanes.each(K * dim * dim, [&](int e) { cov[e] = f.cov[e]; });
+    if (h && post_init) {
+      lanes.each(emrun::post_len(KM, dim), [&](int q) { post_init[q] = post_padding(KM, dim, q); });
+      lanes.sync();
+      lanes.once(K, [&](int k) { init_posterior_state(f, *h, k, post_init); });
+    }
   }
-  out.status = status_of(f.flags);
-  for (int k = 0; k < K; ++k) {
-    prior[k] = f.pi[k];
-    for (int a = 0; a < dim; ++a) mean[k * dim + a] = f.mu[k * dim + a];
-    for (int e = 0; e < dim * dim; ++e) cov[k * dim * dim + e] = f.cov[k * dim * dim + e];
-  }
-  if (h && post_init) {
-    const int PL = emrun::post_len(KM, dim);
-    for (int q = 0; q < PL; ++q) post_init[q] = post_padding(KM, dim, q);
-    for (int k = 0; k < K; ++k) init_posterior_state(f, *h, k, post_init);
-  }
-  return out;
+  return FitResult{f.ll, it > max_iter ? max_iter : it, ill ? kIllConditioned : status_of(f.flags)};
+}
+
+// ---- one whole fit, unit after unit (host builds only): max_obs bounds N as the
+// workspace of a device call does.  A fit that is not valid returns kBadFit and writes
+// nothing; the rest as run_fit's.
+template <int KM>
+inline FitResult run_serial(int K, int dim, int N, int max_obs, const double *x, const int *rows, double reg,
+                            int max_iter, double tolfun, double *prior, double *mean, double *cov, double *lls,
+                            const Hyper *h, double *post_init, const Work &w) {
+  if (!fit_valid(K, KM, N, max_obs, rows)) return FitResult{__builtin_nan(""), 0, kBadFit};
+  Fit<KM> f;
+  return run_fit<KM>(emrun::SerialLanes{}, f, K, dim, N, x, rows, reg, max_iter, tolfun, prior, mean, cov, lls, h,
+                     post_init, w);
 }
 
 }  // namespace gmmrun

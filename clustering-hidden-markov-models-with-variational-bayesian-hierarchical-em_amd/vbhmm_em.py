@@ -397,6 +397,13 @@ FUSED_MAX_K, FUSED_MAX_DIM = 8, 8
 EM_STATUS = ("converged", "max_iter", "unstable", "bad_run")
 
 
+def em_bucket(Ks, over: int = 8) -> int:
+    """The state bucket KM (4 or 8) of the fused kernels for runs or fits of ``Ks`` states;
+    ``over`` where a K passes FUSED_MAX_K (16: a KM the library refuses as unsupported)."""
+    kmax = int(np.max(Ks))
+    return 4 if kmax <= 4 else 8 if kmax <= FUSED_MAX_K else over
+
+
 def em_post_len(KM: int, dim: int) -> int:
     return KM * (3 + KM + dim + dim * dim)
 
@@ -531,7 +538,7 @@ def gmm_fit_batch(subjects, fits, tolfun: float = 1e-5, max_iter: int = 100, kee
     R = len(fits)
     Ks = np.array([int(f[1]) for f in fits], dtype=np.int32)
     if KM is None:
-        KM = 4 if Ks.max() <= 4 else 8 if Ks.max() <= FUSED_MAX_K else 16
+        KM = em_bucket(Ks, over=16)
     rows = np.zeros((R, KM), dtype=np.int32)
     for i, f in enumerate(fits):
         r = np.asarray(f[2], dtype=np.int64).reshape(-1)
@@ -598,7 +605,7 @@ def random_gmm_batch(subjects, Ks, opt: dict, fit_batch=None, hyper: Optional[np
     from . import _capi
     fit = fit_batch if fit_batch is not None else gmm_fit_batch
     Ks = [int(k) for k in np.atleast_1d(Ks)]
-    KM = 4 if max(Ks) <= 4 else 8
+    KM = em_bucket(Ks)
     numtrials = int(opt["numtrials"])
     out, plan, src = {}, {}, {}
     for s, X in enumerate(subjects.X):
@@ -668,7 +675,7 @@ def vbhmm_em_gamma(subjects, items, chunk_runs: int = 0) -> list:
     lib = _capi.lib()
     dim, dev = subjects.dim, subjects.device
     Ks = np.array([len(np.reshape(vp["alpha"], -1)) for _, vp in items])
-    KM = 4 if Ks.max() <= 4 else 8
+    KM = em_bucket(Ks)
     sub = np.array([s for s, _ in items])
     post = np.stack([pack_posterior(vp, K, KM, dim) for (_, vp), K in zip(items, Ks)])
     rn, keep = _em_runs_desc(subjects, sub, Ks, post, KM)
@@ -753,7 +760,7 @@ def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = Fals
     dev = subjects.device
     sub = np.array([int(r[0]) for r in runs])
     Ks = np.array([int(r[1]) for r in runs])
-    KM = 4 if Ks.max() <= 4 else 8 if Ks.max() <= FUSED_MAX_K else 16
+    KM = em_bucket(Ks, over=16)
     PL, SL = em_post_len(KM, dim), em_stats_len(KM, dim)
     if post is None:
         mixes = [_initial_posterior(subjects, s, K, opt, r[2]) for s, K, r in zip(sub, Ks, runs)]
@@ -766,8 +773,7 @@ def vbhmm_em_batch(subjects, runs, opt: dict, device=None, keep_LLs: bool = Fals
         W0inv, W0mode = _w0inv(opt, dim)
     rn, keep = _em_runs_desc(subjects, sub, Ks, post, KM)
     hv = em_hyper_vector(opt, W0inv)
-    hy = _capi.EmHyperT(hv[0], hv[1], hv[2], hv[3], (ctypes.c_double * 8)(*hv[4:12]),
-                        (ctypes.c_double * 8)(*hv[12:20]))
+    hy = _hyper_struct(hv)
     max_iter = int(opt["maxIter"])
     bo = _capi.EmBatchOptT(max_iter, float(opt["minDiff"]), int(chunk_runs))
     R = len(runs)
@@ -960,7 +966,7 @@ def _device_inits(sbt, Ks: list, opt: dict, gmms_list, runs: list, where: list, 
     t0 = time.perf_counter()
     dim, dev = sbt.dim, sbt.device
     copt, _ = vbhmm_clip_hyps(opt)
-    KM = 4 if max(Ks) <= 4 else 8
+    KM = em_bucket(Ks)
     given = {(s, K): list(g[K]) for s, g in enumerate(gmms_list or []) if g is not None for K in Ks if K in g}
     info = {}
     drawn = random_gmm_batch(sbt, Ks, opt, hyper=em_hyper_vector(copt, _w0inv(copt, dim)[0]), info=info,

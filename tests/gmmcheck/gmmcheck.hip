@@ -12,6 +12,8 @@
 #include <vector>
 
 #include "device_pool.h"
+#include "hyper_vec.h"
+#include "vbhmm_batch_launch.h"
 #include "vbhmm_gmm.h"
 #include "vbhmm_gmm_run.h"
 
@@ -64,11 +66,8 @@ int gmmcheck_host(int S, int dim, const int *offsets, const double *x, const int
   if ((KM != 4 && KM != 8) || dim < 1 || dim > kMaxDim || max_iter < 1 || S < 1) return -2;
   Hyper h{};
   if (hyper) {
-    h.alpha0 = hyper[0]; h.epsilon0 = hyper[1]; h.beta0 = hyper[2]; h.v0 = hyper[3];
-    for (int q = 0; q < 8; ++q) {
-      h.m0[q] = hyper[4 + q];
-      h.W0inv[q] = hyper[12 + q];
-    }
+    const vbhmm_em_hyper_t hy = checklib::hyper_struct(hyper);
+    h = vbhem::batch::to_hyper(&hy, dim);
   }
   if (KM == 4)
     host_fits<4>(S, dim, offsets, x, seq_first, R, subject, K, rows, reg, max_iter, tolfun, hyper ? &h : nullptr, prior,
@@ -103,13 +102,7 @@ int gmmcheck_device(int S, int dim, const int *offsets, const double *x, const i
                             static_cast<const int *>(pool.put(rows, (size_t)R * KM * sizeof(int))),
                             static_cast<const double *>(pool.put(reg, (size_t)R * 8))};
   vbhmm_em_hyper_t hy{};
-  if (hyper) {
-    hy.alpha0 = hyper[0]; hy.epsilon0 = hyper[1]; hy.beta0 = hyper[2]; hy.v0 = hyper[3];
-    for (int q = 0; q < 8; ++q) {
-      hy.m0[q] = hyper[4 + q];
-      hy.W0inv_diag[q] = hyper[12 + q];
-    }
-  }
+  if (hyper) hy = checklib::hyper_struct(hyper);
   const vbhmm_gmm_opt_t opt{max_iter, tolfun, chunk_runs};
   const size_t wb = vbhmm_gmm_fit_workspace_bytes(&sb, R, KM, chunk_runs);
   void *ws = pool.put(nullptr, wb);

@@ -10,30 +10,12 @@
 #include <vector>
 
 #include "vbhmm_gmm_run.h"
+#include "walker_input.h"
 
 using namespace vbhem::gmmrun;
+using walker::Lcg;
 
 namespace {
-
-struct Lcg {
-  unsigned long long s;
-  double uni() {
-    s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-    return (double)(s >> 11) / 9007199254740992.0;
-  }
-  double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
-};
-
-Hyper hyper_of(int dim, bool diag) {
-  Hyper h;
-  h.alpha0 = h.epsilon0 = h.beta0 = 1.0;
-  h.v0 = dim + 8.0;
-  for (int a = 0; a < kMaxDim; ++a) {
-    h.m0[a] = 180.0;
-    h.W0inv[a] = diag ? 1000.0 / (1 + a) : 1000.0;
-  }
-  return h;
-}
 
 // mode 0: an ordinary fit; 1: max_iter = 2; 2: one far point among the start rows (ill-
 // conditioned), then the same rows with reg = 1e-10; 3: bad fits; 4: whatever status the
@@ -42,15 +24,12 @@ template <int KM>
 int one_case(int K, int dim, int N, unsigned long long seed, int mode, bool diag = false) {
   Lcg g{seed};
   std::vector<double> x((size_t)N * dim);
-  for (int n = 0; n < N; ++n) {
-    const int z = g.uni() < 0.5;
-    for (int a = 0; a < dim; ++a) x[(size_t)n * dim + a] = (z ? 150.0 : 210.0) + 10.0 * a + 20.0 * g.normal();
-  }
+  walker::two_cluster_draw(g, x.data(), N, dim);
   std::vector<int> rows(KM, 0);
   for (int k = 0; k < K; ++k) rows[k] = k == 0 ? N - 1 : k == 1 ? 0 : (int)((long long)k * N / K);
   if (mode == 2)
     for (int a = 0; a < dim; ++a) x[(size_t)(N - 1) * dim + a] = 1e4;
-  const Hyper h = hyper_of(dim, diag);
+  const Hyper h = walker::test_hyper<Hyper>(dim, diag);
   const int PL = vbhem::emrun::post_len(KM, dim), max_iter = mode == 1 ? 2 : 100;
   std::vector<double> prior(KM, -1.0), mean(KM * dim, -1.0), cov(KM * dim * dim, -1.0), lls(max_iter, 0.0),
       post(PL, -1.0), wp((size_t)N * KM), wl(N);

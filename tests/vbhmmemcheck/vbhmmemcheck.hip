@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "device_pool.h"
+#include "hyper_vec.h"
+#include "vbhmm_batch_launch.h"
 #include "vbhmm_em.h"
 #include "vbhmm_em_run.h"
 
@@ -50,16 +52,6 @@ void host_runs(int dim, const int *offsets, const double *x, const int *seq_firs
   }
 }
 
-Hyper make_hyper(const double *hy) {
-  Hyper h;
-  h.alpha0 = hy[0]; h.epsilon0 = hy[1]; h.beta0 = hy[2]; h.v0 = hy[3];
-  for (int q = 0; q < 8; ++q) {
-    h.m0[q] = hy[4 + q];
-    h.W0inv[q] = hy[12 + q];
-  }
-  return h;
-}
-
 }  // namespace
 
 extern "C" {
@@ -74,7 +66,8 @@ int vbhmmemcheck_host(int S, int dim, const int *offsets, const double *x, const
     if (K[r] < 1 || K[r] > KM || subject[r] < 0 || subject[r] >= S) return -2;
   int max_seqs, max_obs;
   subject_maxima(S, offsets, seq_first, &max_seqs, &max_obs);
-  const Hyper h = make_hyper(hyper);
+  const vbhmm_em_hyper_t hy = checklib::hyper_struct(hyper);
+  const Hyper h = vbhem::batch::to_hyper(&hy, dim);
   if (KM == 4)
     host_runs<4>(dim, offsets, x, seq_first, R, subject, K, post_in, h, max_iter, min_diff, post_out, post_estep,
                  stats, LL, iters, status, LLs, max_seqs, max_obs);
@@ -104,12 +97,7 @@ int vbhmmemcheck_device(int S, int dim, const int *offsets, const double *x, con
   vbhmm_em_runs_t rn{R, KM, static_cast<const int *>(pool.put(subject, (size_t)R * sizeof(int))),
                      static_cast<const int *>(pool.put(K, (size_t)R * sizeof(int))),
                      static_cast<const double *>(pool.put(post_in, (size_t)R * PL * 8))};
-  vbhmm_em_hyper_t hy{};
-  hy.alpha0 = hyper[0]; hy.epsilon0 = hyper[1]; hy.beta0 = hyper[2]; hy.v0 = hyper[3];
-  for (int q = 0; q < 8; ++q) {
-    hy.m0[q] = hyper[4 + q];
-    hy.W0inv_diag[q] = hyper[12 + q];
-  }
+  const vbhmm_em_hyper_t hy = checklib::hyper_struct(hyper);
   const vbhmm_em_opt_t opt{max_iter, min_diff, chunk_runs};
   const size_t wb = vbhmm_em_batch_workspace_bytes(&sb, R, KM, chunk_runs);
   void *ws = pool.put(nullptr, wb);

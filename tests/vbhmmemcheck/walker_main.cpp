@@ -9,19 +9,12 @@
 #include <vector>
 
 #include "vbhmm_em_run.h"
+#include "walker_input.h"
 
 using namespace vbhem::emrun;
+using walker::Lcg;
 
 namespace {
-
-struct Lcg {
-  unsigned long long s;
-  double uni() {
-    s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-    return (double)(s >> 11) / 9007199254740992.0;
-  }
-  double normal() { return std::sqrt(-2.0 * std::log(uni() + 1e-300)) * std::cos(6.283185307179586 * uni()); }
-};
 
 // empties: sequences 0, N / 2, N / 2 + 1 and N - 1 have no observation; diag: W0inv is
 // 1000 / (1 + a) instead of 1000
@@ -36,17 +29,8 @@ int one_case(int K, int dim, int N, int maxlen, unsigned long long seed, bool br
   }
   const int obs = off[N];
   std::vector<double> x((size_t)obs * dim);
-  for (int p = 0; p < obs; ++p) {
-    const int z = g.uni() < 0.5;
-    for (int a = 0; a < dim; ++a) x[(size_t)p * dim + a] = (z ? 150.0 : 210.0) + 10.0 * a + 20.0 * g.normal();
-  }
-  Hyper h;
-  h.alpha0 = h.epsilon0 = h.beta0 = 1.0;
-  h.v0 = dim + 8.0;
-  for (int a = 0; a < kMaxDim; ++a) {
-    h.m0[a] = 180.0;
-    h.W0inv[a] = diag ? 1000.0 / (1 + a) : 1000.0;
-  }
+  walker::two_cluster_draw(g, x.data(), obs, dim);
+  const Hyper h = walker::test_hyper<Hyper>(dim, diag);
   const int PL = post_len(KM, dim), SL = stats_len(KM, dim);
   std::vector<double> post(PL, 1.0), est(PL), st(SL), LLs(30, 0.0);
   double *alpha = post.data(), *eps = alpha + KM, *beta = eps + KM * KM, *v = beta + KM, *m = v + KM,

@@ -9,18 +9,12 @@
 #include <vector>
 
 #include "vbhem_wtk_run.h"
+#include "walker_input.h"
 
 using namespace vbhem::wtkrun;
+using walker::Lcg;
 
 namespace {
-
-struct Lcg {
-  unsigned long long s;
-  double uni() {
-    s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-    return (double)(s >> 11) / 9007199254740992.0;
-  }
-};
 
 // mode 0: ordinary; 1: every point the same (degenerate); 2: a NaN coordinate; 3: j0 = n;
 // 4: every second weight zero
