@@ -6,7 +6,7 @@ ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function
 LIBDIR   := $(PKG)/lib
 SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_stats.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_dic.hip $(PKG)/csrc/vbhmm_em.hip $(PKG)/csrc/vbhmm_gmm.hip $(PKG)/csrc/vbhem_wtk.hip
-HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h $(PKG)/csrc/vbhmm_hmmset.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h include/vbhmm_em.h $(PKG)/csrc/vbhmm_em_run.h include/vbhmm_gmm.h $(PKG)/csrc/vbhmm_gmm_run.h include/vbhem_init.h $(PKG)/csrc/vbhem_wtk_run.h $(PKG)/csrc/vbhem_special.h $(PKG)/csrc/vbhmm_batch_launch.h
+HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_list4_slots.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h $(PKG)/csrc/vbhmm_hmmset.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h include/vbhmm_em.h $(PKG)/csrc/vbhmm_em_run.h include/vbhmm_gmm.h $(PKG)/csrc/vbhmm_gmm_run.h include/vbhem_init.h $(PKG)/csrc/vbhem_wtk_run.h $(PKG)/csrc/vbhem_special.h $(PKG)/csrc/vbhmm_batch_launch.h
 OBJS     := $(patsubst $(PKG)/csrc/%.hip,$(LIBDIR)/%.o,$(SRCS))
 CHECKS   := mathcheck scorecheck ppkcheck ccfdcheck diccheck vbhmmemcheck gmmcheck wtkcheck
 CHECK_HDRS := $(wildcard tests/checklib/*.h)

@@ -56,7 +56,8 @@ thread_local TimingState g_timing;
 
 // the kernels the last call of this host thread ran for its recursion passes
 // (vbhem_last_kernel: what a benchmark line names, taken from the launch itself)
-thread_local std::string g_last_kernel[2];
+// ([2]: the fused call's gated statistics kernel family)
+thread_local std::string g_last_kernel[3];
 std::string split_name(const vbhem::SplitArgs &a) {
   return "vbhem::fb_split_kernel<" + std::to_string(a.S) + ", " + std::to_string(a.lpc) + ", " +
          std::to_string(a.mode) + ">";
@@ -417,6 +418,7 @@ struct FusedWs {
   double *scratch, *nu1, *xi, *tnu, *Z, *slabs;
   double *E, *W, *bias, *shift;
   double *U;                        // per-call operand of the emission GEMM (null: prepared)
+  double *l4parts;                  // fb_list4_kernel's statistics partials (null: not its shape)
 };
 
 size_t carve_fused(void *ws, const vbhem_base_t *b, const vbhem_cluster_t *c, int T, FusedWs &w,
@@ -454,6 +456,13 @@ size_t carve_fused(void *ws, const vbhem_base_t *b, const vbhem_cluster_t *c, in
   w.list_tot = cv.take<int>((size_t)K);
   // A' [K][S][S] (read-only for every recursion kernel)
   w.Atg = cv.take<double>((size_t)K * S * S);
+  // the accumulating gate-list pass's partials: a slot per wave of its grid (at most the
+  // inline fallback's kExactThreads) and cluster (vbhem_list4_slots.h)
+  const int NU = (int)vbhem_stats_nu(b->d, b->covmode);
+  w.l4parts = vbhem::list4_acc_supported(S, SB, T, K, NU)
+                  ? cv.take<double>((size_t)vbhem::l4s_max_slots(kExactThreads, K) *
+                                    vbhem::l4s_part_len(S, vbhem::us_nup(NU)))
+                  : nullptr;
   // the exact fallback's scratch last: its size does not move the hot buffers
   w.scratch = cv.take<double>(exact_stride(S, SB, T) * kExactThreads);
   return cv.off + 256;
@@ -587,7 +596,9 @@ unsigned list_grid(const vbhem::SplitArgs &a, size_t lds) {
 int run_fb_list(const FbCtx &c, int i_begin, int i_end, int i_buf0, double *nu1, double *xi,
                 double *tnu, const double *Ebuf, long long e_ld, const int *list,
                 const int *list_tot, int list_cap, int *flags, double *scratch, double *LL,
-                hipStream_t st, bool fold = false, bool *inlined = nullptr) {
+                hipStream_t st, bool fold = false, bool *inlined = nullptr,
+                const vbhem::StatsArgs *acc_sa = nullptr, double *acc_parts = nullptr,
+                int *acc_waves = nullptr) {
   if (i_end <= i_begin) return VBHEM_OK;
   // flags[0] is zero here: the backward pass's fb_exact_kernel reset it
   if (!c.split.lds_l) return fail(VBHEM_ERR_UNSUPPORTED, "gate-list pass does not fit LDS");
@@ -601,8 +612,17 @@ int run_fb_list(const FbCtx &c, int i_begin, int i_end, int i_buf0, double *nu1,
   // folded fallback: the list kernel recomputes its own flagged pairs when its
   // persistent grid has a scratch slot per wavefront (then no launch after the pass)
   ca.xinline = 0;
+  // fb_list4_kernel's statistics-accumulating variant (acc_sa: this group's statistics
+  // arguments): the weights, the statistics copy of a prepared operand and a shape within
+  // its tiles; it needs the inline fallback, which it may take without the fold as well
+  // (several base groups) unless the fold was switched off
+  const vbhem::Switches &sw = vbhem::switches();
+  const bool acc = c.list4 && acc_sa && acc_parts && acc_sa->Us && acc_sa->Z && !acc_sa->vhem &&
+                   vbhem::list4_acc_supported(ca.S, ca.SB, ca.T, ca.K, acc_sa->NU) &&
+                   !sw.NO_LIST4_STATS && !sw.NO_STATS_M && !sw.NO_STATS_U;
+  if (acc_waves) *acc_waves = 0;
   auto set_inline = [&](long long waves) {
-    if (!fold || waves > kExactThreads || vbhem::switches().NO_LIST_INLINE) return;
+    if (!(fold || (acc && !sw.NO_FOLD_EXACT)) || waves > kExactThreads || sw.NO_LIST_INLINE) return;
     ca.xinline = 1;
     ca.xscr = scratch;
     ca.xstride = (long long)exact_stride(c.plan.a.S, c.plan.a.SB, c.plan.a.T);
@@ -616,8 +636,17 @@ int run_fb_list(const FbCtx &c, int i_begin, int i_end, int i_buf0, double *nu1,
   hipError_t e;
   if (c.list4) {  // S = 8, SB <= 8, T = 10: fb_list4_kernel (MFMA), one wave per quad item
     ca.Atg = c.bwd.a.Atg;
-    const unsigned grid = (unsigned)(vbhem::device_cus() * std::max(1, vbhem::list4_resident_blocks()));
+    unsigned grid = (unsigned)(vbhem::device_cus() * std::max(1, vbhem::list4_resident_blocks(acc)));
     set_inline(vbhem::list4_inline_waves(ca, grid));
+    if (acc && ca.xinline) {
+      ca.acc = 1;
+      ca.acc_nup = vbhem::us_nup(acc_sa->NU);
+      ca.accZ = acc_sa->Z; ca.accUs = acc_sa->Us; ca.acc_parts = acc_parts;
+      if (acc_waves) *acc_waves = (int)vbhem::list4_inline_waves(ca, grid);
+    } else if (acc) {  // no inline fallback: the per-pair outputs, on that kernel's grid
+      grid = (unsigned)(vbhem::device_cus() * std::max(1, vbhem::list4_resident_blocks()));
+      if (fold) set_inline(vbhem::list4_inline_waves(ca, grid));  // (that path inlines under the fold only)
+    }
     e = vbhem::launch_list4(ca, grid, st);
     if (e != hipSuccess) return hip_fail(e, "fb_list4_kernel");
     g_last_kernel[1] = "vbhem::fb_list4_kernel<" + std::to_string(ca.T) +
@@ -799,7 +828,7 @@ const char *vbhem_last_error(void) { return g_err.c_str(); }
 size_t vbhem_debug_extra_lds(size_t bytes) { return g_debug_extra_lds.exchange(bytes); }
 
 const char *vbhem_last_kernel(int pass) {
-  return (pass == 0 || pass == 1) ? g_last_kernel[pass].c_str() : "";
+  return (pass >= 0 && pass <= 2) ? g_last_kernel[pass].c_str() : "";
 }
 
 const char *vbhem_version(void) { return "vbhem-mi355x 0.1.0 (gfx950)"; }
@@ -1136,13 +1165,22 @@ static int fused_impl(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
       if (e != hipSuccess) return hip_fail(e, "gate_list_kernel");
       if (ev0) g_timing.stats.emplace_back(ev0, timing_event(st));
       bool inl = false;
+      int l4w = 0;  // > 0: fb_list4_kernel accumulated the statistics, on that many waves
       rc = run_fb_list(ctx, g0, g1, g0, w.nu1, w.xi, w.tnu, w.E, e_ld, w.list, w.list_tot,
-                       w.group, w.flags, w.scratch, LL_elbo_dev, st, fold, &inl);
+                       w.group, w.flags, w.scratch, LL_elbo_dev, st, fold, &inl, &sa, w.l4parts, &l4w);
       if (rc != VBHEM_OK) return rc;
       if (fold) sa.fold = inl ? 2 : 1;  // 2: no fb_exact_kernel launch before the statistics
       ev0 = timing_on(st) ? timing_event(st) : nullptr;
       int ss = nchunk;
-      e = vbhem::launch_stats_list(sa, nchunk, sl_lds, st, &ss);
+      if (l4w > 0) {
+        ss = 1;
+        g_last_kernel[2] = "vbhem::list4_stats_reduce_kernel";
+        e = vbhem::launch_list4_stats_reduce(sa, w.l4parts, l4w, st);
+        if (e != hipSuccess) return hip_fail(e, "list4_stats_reduce_kernel");
+      } else {
+        g_last_kernel[2] = "vbhem::stats_list_kernels";
+        e = vbhem::launch_stats_list(sa, nchunk, sl_lds, st, &ss);
+      }
       if (e != hipSuccess) return hip_fail(e, "stats_list_kernel");
       if (g0 == 0) stats_slabs = ss;  // later groups add into [0, ss) with ss <= this
     } else {

@@ -25,6 +25,15 @@
 // inputs); a flagged pair is recomputed by the wave itself after its item loop
 // (xinline: queued in LDS; no fb_exact_kernel launch after the pass) or by the exact
 // kernel.
+// The sums (ACC; SplitArgs::acc, needs xinline): instead of the per-pair outputs the wave
+// accumulates the gated statistics of its items in LDS -- Z nu_1, Z (A' o H) and, on the
+// matrix cores, (Z sum_t_nu) Us against the base's statistic features (the quad's tnT
+// blocks are the A operands as they stand, a 512-byte segment of Us the B operand of all
+// four MFMA blocks, one pair's A copied to the four blocks by ds_bpermute) -- over a
+// contiguous range of items, and flushes one partial per cluster of the range
+// (vbhem_list4_slots.h) for list4_stats_reduce_kernel.  A flagged pair is added from its
+// exact values, by the wave that queued it.  C4: list pass 0.208 -> 0.226 ms, statistics
+// kernels 0.153 -> 0.049 ms (profiles/r07a_ab_c4_list4_stats.txt).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,11 +60,118 @@ constexpr int kL4T = 10;      // the tau this kernel is built for (C3 - C5)
 }  // namespace
 constexpr int kL4XQ = 1024;   // flagged pairs queued per wave (xinline; list4_xq_fits)
 namespace {
+// ACC: a wave's accumulators in LDS, doubles: the (Z sum_t_nu) Us tiles [2 I][3 F'][64
+// lanes] and Z (A' o H) [2 I][2 I'][64 lanes] in the lanes that compute them, then Z nu_1
+// [2 I][4 r][4 pairs] and the item's own nu_1 sums (kept from K3 to the epilogue here,
+// not in registers)
+constexpr int kL4AccM = 2 * kL4sMaxTiles * 64, kL4AccN = kL4AccM + 4 * 64, kL4AccS = kL4AccN + 32;
+constexpr int kL4AccLen = kL4AccS + 32;
+// the forward steps at which the Us operands of pairs 0, 1 and of pairs 2, 3 are
+// requested (T1 >= T: after the sweep); build switches for A/B
+#ifndef VBHEM_L4_US_T0
+#define VBHEM_L4_US_T0 8
+#endif
+#ifndef VBHEM_L4_US_T1
+#define VBHEM_L4_US_T1 10
+#endif
+
+// ---- ACC: the sums of fb_list4_kernel<T, FAST, true> (lane = 16 r + 4 b + c) ----
+// a wave's own LDS exchange: program order, writes visible to its other lanes
+__device__ __forceinline__ void l4_wsync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// base i's statistic features as the B operands of the tile MFMAs: ub[F'][J] = element
+// `lane` of the 512-byte segment (feature tile F', base states 4 J .. 4 J + 3) of its Us
+// block, i.e. Us(b = 4 J + r, f = 16 F' + 4 q + c) in block q.  Tiles and slices the
+// shape does not have repeat an existing one (no branch around a load; their products
+// are never flushed, or meet a zero A operand)
+__device__ __forceinline__ void l4_load_us(const SplitArgs &p, int i, int sbp, int ntile, int lane,
+                                           double (&ub)[kL4sMaxTiles][2]) {
+  const double *us = p.accUs + (size_t)i * sbp * p.acc_nup + lane;
+#pragma unroll
+  for (int f = 0; f < kL4sMaxTiles; ++f)
+#pragma unroll
+    for (int J = 0; J < 2; ++J) ub[f][J] = us[((f < ntile ? f : ntile - 1) * sbp + (4 * J < sbp ? 4 * J : 0)) * 16];
+}
+// U tile (I, F') += sum over the NP pair slots and J of (Z tn)^T block (J, I) of the pair,
+// copied into all four MFMA blocks, times ub[pair][F'][J]: lane (r, q, c) holds
+// (sigma = 4 I + r, f = 16 F' + 4 q + c).  za: this lane's pair's Z tn^T blocks, zero
+// where the pair does not count
+template <int NP>
+__device__ __forceinline__ void l4_acc_u(double *accw, const double (&za)[2][2],
+                                         const double (&ub)[NP][kL4sMaxTiles][2], int r, int c, int lane) {
+  double acc[2][kL4sMaxTiles];
+#pragma unroll
+  for (int I = 0; I < 2; ++I)
+#pragma unroll
+    for (int f = 0; f < kL4sMaxTiles; ++f) acc[I][f] = accw[(I * kL4sMaxTiles + f) * 64 + lane];
+#pragma unroll
+  for (int pp = 0; pp < NP; ++pp) {
+    const int src = (16 * r + 4 * pp + c) << 2;
+#pragma unroll
+    for (int J = 0; J < 2; ++J)
+#pragma unroll
+      for (int I = 0; I < 2; ++I) {
+        const double xa = bperm_d(src, za[J][I]);
+#pragma unroll
+        for (int f = 0; f < kL4sMaxTiles; ++f) acc[I][f] = mfma4(xa, ub[pp][f][J], acc[I][f]);
+      }
+  }
+#pragma unroll
+  for (int I = 0; I < 2; ++I)
+#pragma unroll
+    for (int f = 0; f < kL4sMaxTiles; ++f) accw[(I * kL4sMaxTiles + f) * 64 + lane] = acc[I][f];
+}
+// Z nu_1 (lanes c == 0: sigma = 4 I + r of pair b) and Z (A' o H) (every lane: (4 I + r,
+// 4 I' + c) of pair b), kept per pair slot
+__device__ __forceinline__ void l4_acc_nm(double *accw, const double (&n1)[2], const double (&xm)[2][2],
+                                          int r, int b, int c, int lane) {
+#pragma unroll
+  for (int I = 0; I < 2; ++I) {
+    if (c == 0) accw[kL4AccN + 16 * I + 4 * r + b] += n1[I];
+#pragma unroll
+    for (int I2 = 0; I2 < 2; ++I2) accw[kL4AccM + (2 * I + I2) * 64 + lane] += xm[I][I2];
+  }
+}
+// the wave's sums to partial `slot` (U [S][NUP] | N1 [S] | M [S][S]; written, or added by
+// the lanes that wrote it), the pair slots of N1 and M folded in slot order; zeroed after
+__device__ __forceinline__ void l4_flush(const SplitArgs &p, double *accw, int slot, bool add, int ntile,
+                                         int lane) {
+  constexpr int S = 8;
+  const int nup = p.acc_nup, r = lane >> 4, b = (lane >> 2) & 3, c = lane & 3;
+  double *part = p.acc_parts + (size_t)slot * l4s_part_len(S, nup);
+  auto put = [add](double *dst, double v) { *dst = add ? *dst + v : v; };
+#pragma unroll
+  for (int I = 0; I < 2; ++I)
+#pragma unroll
+    for (int f = 0; f < kL4sMaxTiles; ++f) {
+      double *a = accw + (I * kL4sMaxTiles + f) * 64 + lane;
+      if (f < ntile) put(part + (4 * I + r) * nup + 16 * f + 4 * b + c, *a);
+      *a = 0.0;
+    }
+  l4_wsync();
+  {  // M entry (sigma, sigma') = (lane >> 3, lane & 7)
+    const double *a = accw + kL4AccM + (2 * (lane >> 5) + ((lane >> 2) & 1)) * 64 + 16 * ((lane >> 3) & 3) + (lane & 3);
+    put(part + S * nup + S + lane, ((a[0] + a[4]) + a[8]) + a[12]);
+  }
+  if (lane < S) {  // N1 entry sigma = lane
+    const double *a = accw + kL4AccN + 16 * (lane >> 2) + 4 * (lane & 3);
+    put(part + S * nup + lane, ((a[0] + a[1]) + a[2]) + a[3]);
+  }
+  l4_wsync();
+#pragma unroll
+  for (int x = 0; x < 4; ++x) accw[kL4AccM + 64 * x + lane] = 0.0;
+  if (lane < 32) accw[kL4AccN + lane] = 0.0;
+  l4_wsync();
+}
 }  // namespace
 
 // FAST: SB == 8 (no clamp or zero select in the item's addresses and operands) and
 // 32-bit load offsets (A, the prior and E below 4 GB), as fb_bwd4_kernel<O32>
-template <int T, bool FAST>
+// ACC: the gated statistics accumulated here (SplitArgs::acc; the header's "sums" below)
+template <int T, bool FAST, bool ACC>
 __global__ __launch_bounds__(64 * kL4NWB) __attribute__((amdgpu_waves_per_eu(kL4Waves)))
 void fb_list4_kernel(const SplitArgs p) {
   constexpr int S = 8;
@@ -64,8 +180,11 @@ void fb_list4_kernel(const SplitArgs p) {
   __shared__ int pre[kList4MaxK + 1];  // first quad item of every cluster
   __shared__ int tots[kList4MaxK];     // the gate lists' lengths
   __shared__ int xq[kL4NWB * kL4XQ];   // per wave: its flagged pairs (xinline)
+  __shared__ __attribute__((aligned(16))) double accs[ACC ? kL4NWB * kL4AccLen : 1];
   const int tid = threadIdx.x;
   stage_tables(etab, ltab, tid, 64 * kL4NWB);
+  if constexpr (ACC)  // every wave's sums
+    for (int x = tid; x < kL4NWB * kL4AccLen; x += 64 * kL4NWB) accs[x] = 0.0;
   const int K = p.K, SB = FAST ? 8 : p.SB;
   using off_t_ = typename std::conditional<FAST, unsigned, size_t>::type;
   auto ld = [](const double *base, off_t_ x) {
@@ -87,7 +206,10 @@ void fb_list4_kernel(const SplitArgs p) {
   __syncthreads();
   const int nitem = __builtin_amdgcn_readfirstlane(pre[K]);
   const double vlim = kVMax / (double)T - 3.0;
-  const int gw = (int)blockIdx.x * kL4NWB + (tid >> 6), nw = (int)gridDim.x * kL4NWB;
+  // (ACC: the wave index in an SGPR -- its item range and slots are scalar then)
+  const int gw = ACC ? __builtin_amdgcn_readfirstlane((int)blockIdx.x * kL4NWB + (tid >> 6))
+                     : (int)blockIdx.x * kL4NWB + (tid >> 6),
+            nw = (int)gridDim.x * kL4NWB;
 
   // An item's global inputs (A in both layouts, E, the prior) are loaded during the
   // previous item's forward sweep, once its first lattice slices are dead (no extra
@@ -131,14 +253,19 @@ void fb_list4_kernel(const SplitArgs p) {
   int js = 0, jsn = 0, nq = 0;
   ItemIn cur;
   int icur = 0;
-  if (gw < nitem) {
+  // the wave's items: gw, gw + nw, ...; ACC: the contiguous range [gw per, (gw + 1) per)
+  // (vbhem_list4_slots.h), so that its sums change cluster, and are flushed, rarely
+  const int per = ACC ? l4s_per_wave(nitem, nw) : 1;
+  const int it0 = ACC ? gw * per : gw, itend = ACC ? min(nitem, it0 + per) : nitem;
+  const int istep = ACC ? 1 : nw;
+  if (it0 < itend) {
     const int lane = tid & 63;
-    while (pre[js + 1] <= gw) ++js;
+    while (pre[js + 1] <= it0) ++js;
     jsn = js;
-    icur = base_of(gw, __builtin_amdgcn_readfirstlane(js), (lane >> 2) & 3);
+    icur = base_of(it0, __builtin_amdgcn_readfirstlane(js), (lane >> 2) & 3);
     load_in(icur, __builtin_amdgcn_readfirstlane(js), lane >> 4, lane & 3, cur);
   }
-  for (int it = gw; it < nitem; it += nw) {
+  for (int it = it0; it < itend; it += istep) {
     // lane geometry recomputed per item from an opaque copy of the thread id, so that
     // no lane-invariant address is hoisted out of the item loop (such live ranges
     // spilled to scratch at 256 VGPRs)
@@ -146,12 +273,13 @@ void fb_list4_kernel(const SplitArgs p) {
     asm volatile("" : "+v"(tq));
     const int lane = tq & 63;
     const int r = lane >> 4, b = (lane >> 2) & 3, c = lane & 3;
+    double *const accw = accs + (ACC ? (tq >> 6) * kL4AccLen : 0);  // ACC: this wave's sums
     const int qsrc0 = (4 * b + r) << 2, qsrc1 = (16 + 4 * b + r) << 2;
     const int taddr = (16 * c + 4 * b + r) << 2;
     const unsigned long long pmask = 0x000F000F000F000Full << (4 * b);
     const int j = __builtin_amdgcn_readfirstlane(js);  // (js: advanced to it)
     // the next item (a repeat of this one past the end): its cluster and list entry now
-    const int itn = min(it + nw, nitem - 1);
+    const int itn = min(it + istep, itend - 1);
     while (pre[jsn + 1] <= itn) ++jsn;
     const int jn = __builtin_amdgcn_readfirstlane(jsn);
     const int inext = base_of(itn, jn, b);
@@ -318,7 +446,11 @@ void fb_list4_kernel(const SplitArgs p) {
         double a = nu[i2][0] + nu[i2][1];
         a += shfl_xor_d(a, 1);
         a += shfl_xor_d(a, 2);
-        if (act && c == 0) p.nu1[lp * S + 4 * i2 + r] = a;
+        if constexpr (ACC) {
+          if (c == 0) accw[kL4AccS + 16 * i2 + 4 * r + b] = a;  // (read back by this lane)
+        } else {
+          if (act && c == 0) p.nu1[lp * S + 4 * i2 + r] = a;
+        }
       }
     }
 
@@ -332,6 +464,11 @@ void fb_list4_kernel(const SplitArgs p) {
         AbF[j2][jj] = (be < SB && bp < SB) ? cur.af[j2][jj] : 0.0;
       }
     ItemIn nxt;
+    // ACC: the pair's weight, and the four bases' Us operands: loaded into the registers
+    // of dead lattice slices during the last forward steps (two pairs) and after them
+    double zc = 0.0, ub[ACC ? 4 : 1][kL4sMaxTiles][2];
+    const int sbp = us_sbp(SB), ntile = ACC ? p.acc_nup / 16 : 1;
+    if constexpr (ACC) zc = p.accZ[lp];
     double nuT[2][2], tnT[2][2], H[2][2];
     transpose8(nu, nuT, taddr);
 #pragma unroll
@@ -345,6 +482,16 @@ void fb_list4_kernel(const SplitArgs p) {
     for (int t = 1; t < T; ++t) {
       // the next item's inputs, into the registers of the lattice slices 1 .. T/2 - 1
       if (t == T / 2) load_in(inext, jn, r, c, nxt);
+      if constexpr (ACC)
+        if (t == VBHEM_L4_US_T0) {
+          l4_load_us(p, __builtin_amdgcn_readlane(i, 0), sbp, ntile, lane, ub[0]);
+          l4_load_us(p, __builtin_amdgcn_readlane(i, 4), sbp, ntile, lane, ub[1]);
+        }
+      if constexpr (ACC)
+        if (t == VBHEM_L4_US_T1) {
+          l4_load_us(p, __builtin_amdgcn_readlane(i, 8), sbp, ntile, lane, ub[2]);
+          l4_load_us(p, __builtin_amdgcn_readlane(i, 12), sbp, ntile, lane, ub[3]);
+        }
       double Gt[2][2];
       transpose8(lat[t], Gt, taddr);
       // f^T block (J, I) = sum_J' Ab(J', J)^T nu^T(J', I); Z^T block (J, I') as the backward's
@@ -385,7 +532,32 @@ void fb_list4_kernel(const SplitArgs p) {
     // ---- outputs and fallback flags ----
     const bool pbad = (__ballot(bad) & pmask) != 0;
     const bool pnf = cl_nf || (__ballot(nfp) & pmask) != 0;
-    if (act) {
+    if constexpr (ACC) {
+      // the sums: a pair slot past the list's end, or flagged for the exact recursion
+      // (counted below from its exact values), has its operands selected to zero -- not
+      // multiplied: a flagged pair's fast values may be non-finite
+      if (VBHEM_L4_US_T1 >= T) {
+        l4_load_us(p, __builtin_amdgcn_readlane(i, 8), sbp, ntile, lane, ub[2]);
+        l4_load_us(p, __builtin_amdgcn_readlane(i, 12), sbp, ntile, lane, ub[3]);
+      }
+      const bool use = act && !(pbad && !pnf);
+      double za[2][2], xm[2][2], n1[2];
+#pragma unroll
+      for (int x = 0; x < 2; ++x) {
+        n1[x] = use ? zc * accw[kL4AccS + 16 * x + 4 * r + b] : 0.0;
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+          // tnT block (J = x, I = y): beta = 4 x + r; H block (I = x, I' = y)
+          za[x][y] = (use && (FAST || 4 * x + r < SB)) ? zc * tnT[x][y] : 0.0;
+          xm[x][y] = use ? zc * (Ap[x][y] * H[x][y]) : 0.0;
+        }
+      }
+      l4_acc_nm(accw, n1, xm, r, b, c, lane);
+      l4_acc_u<4>(accw, za, ub, r, c, lane);
+      if (act && pbad && !pnf && lane == 4 * b) atomicAdd(p.flag_count + 1, 1);
+      // the sums leave the wave at a cluster boundary and after its last item
+      if (it + 1 >= itend || jn != j) l4_flush(p, accw, l4s_slot(it, j, per), false, ntile, lane);
+    } else if (act) {
       // sum_t_nu[sigma][beta]: tnT block (J, I) lane (r, b, c) = tn[4I + c][4J + r]
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj)
@@ -414,7 +586,8 @@ void fb_list4_kernel(const SplitArgs p) {
       const unsigned long long fm = __ballot(act && pbad && !pnf && lane == 4 * b);
       if (fm) {
         const int l = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(fm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)fm, 0u));
-        if (fm >> lane & 1) xq[(tid >> 6) * kL4XQ + nq + l] = (int)((size_t)i * K + j);
+        // (ACC: from the opaque copy -- the hoisted queue address was spilled to scratch)
+        if (fm >> lane & 1) xq[((ACC ? tq : tid) >> 6) * kL4XQ + nq + l] = (int)((size_t)i * K + j);
         nq += __builtin_popcountll(fm);
       }
     }
@@ -427,8 +600,42 @@ void fb_list4_kernel(const SplitArgs p) {
   // wave), after the item loop, where none of the loop's registers are live
   if (p.xinline) {
     const int *q = xq + (tid >> 6) * kL4XQ;
-    for (int x = 0; x < nq; ++x)
-      exact_pair_wave<true>(p.xf, __builtin_amdgcn_readfirstlane(q[x]), p.xscr + (size_t)gw * p.xstride, nullptr);
+    for (int x = 0; x < nq; ++x) {
+      const int pair = __builtin_amdgcn_readfirstlane(q[x]);
+      exact_pair_wave<true>(p.xf, pair, p.xscr + (size_t)gw * p.xstride, nullptr);
+      if constexpr (ACC) {
+        // ACC: the pair's exact nu_1, xi and sum_t_nu read back from the workspace (other
+        // lanes' stores: device-scope fence) as pair slot 0 of a quad and added to the
+        // partial of its cluster, which the item loop wrote: counted once, in queue order
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        __builtin_amdgcn_wave_barrier();
+        int tq = tid;
+        asm volatile("" : "+v"(tq));
+        const int lane = tq & 63, r = lane >> 4, b = (lane >> 2) & 3, c = lane & 3;
+        double *const accw = accs + (tq >> 6) * kL4AccLen;
+        const int i = pair / K, j = pair - i * K;
+        const size_t lp = (size_t)(i - p.i_buf0) * K + j;
+        const int sbp = us_sbp(SB), ntile = p.acc_nup / 16;
+        const bool on = b == 0;
+        const double zc = p.accZ[lp];
+        double ub[1][kL4sMaxTiles][2], za[2][2], xm[2][2], n1[2];
+        l4_load_us(p, i, sbp, ntile, lane, ub[0]);
+#pragma unroll
+        for (int x2 = 0; x2 < 2; ++x2) {
+          n1[x2] = on ? zc * p.nu1[lp * S + 4 * x2 + r] : 0.0;
+#pragma unroll
+          for (int y = 0; y < 2; ++y) {
+            const bool tv = on && 4 * x2 + r < SB;
+            za[x2][y] = tv ? zc * p.tnu[(lp * S + 4 * y + c) * SB + 4 * x2 + r] : 0.0;
+            xm[x2][y] = on ? zc * p.xi[(lp * S + 4 * x2 + r) * S + 4 * y + c] : 0.0;
+          }
+        }
+        l4_acc_nm(accw, n1, xm, r, b, c, lane);
+        l4_acc_u<1>(accw, za, ub, r, c, lane);
+        const int jx = x + 1 < nq ? __builtin_amdgcn_readfirstlane(q[x + 1]) % K : -1;
+        if (jx != j) l4_flush(p, accw, gw + j, true, ntile, lane);
+      }
+    }
   }
 }
 
@@ -447,15 +654,42 @@ long long list4_inline_waves(const SplitArgs &a, unsigned grid) {
   if (nw < 1 || 4 * ((items + nw - 1) / nw) > kL4XQ) return 1ll << 40;
   return nw;
 }
-int list4_resident_blocks() {
-  auto *fn = &fb_list4_kernel<kL4T, true>;
+bool list4_acc_supported(int S, int SB, int T, int K, int NU) {
+  return list4_supported(S, SB, T, K) && us_nup(NU) <= 16 * kL4sMaxTiles;
+}
+int list4_resident_blocks(bool acc) {
+  auto *fn = acc ? &fb_list4_kernel<kL4T, true, true> : &fb_list4_kernel<kL4T, true, false>;
   return resident_per_cu(reinterpret_cast<const void *>(fn), 64 * kL4NWB, 0);
 }
 hipError_t launch_list4(const SplitArgs &a, unsigned grid, hipStream_t st) {
   if (!list4_supported(a.S, a.SB, a.T, a.K) || !a.Atg || !a.list || !a.list_tot) return hipErrorInvalidValue;
-  auto *fn = list4_fast(a) ? &fb_list4_kernel<kL4T, true> : &fb_list4_kernel<kL4T, false>;
+  auto *fn = list4_fast(a) ? &fb_list4_kernel<kL4T, true, false> : &fb_list4_kernel<kL4T, false, false>;
+  if (a.acc) {
+    // the sums need the inline fallback (a flagged pair is added from its exact values by
+    // the wave that queued it), the operands and a partial per slot of this grid
+    if (!a.xinline || !a.accZ || !a.accUs || !a.acc_parts || a.acc_nup < 16 || a.acc_nup % 16 ||
+        a.acc_nup > 16 * kL4sMaxTiles)
+      return hipErrorInvalidValue;
+    fn = list4_fast(a) ? &fb_list4_kernel<kL4T, true, true> : &fb_list4_kernel<kL4T, false, true>;
+  }
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * kL4NWB), 0, st, a);
   return hipGetLastError();
 }
 
 }  // namespace vbhem
+
+extern "C" int vbhem_list4_stats_slot_plan(const int *tot, int K, int nw, int *per, int *first,
+                                           int *count) {
+  int nitem = 0;
+  for (int j = 0; j < K; ++j) nitem += vbhem::l4s_items(tot[j]);
+  const int pw = vbhem::l4s_per_wave(nitem, nw);
+  if (per) *per = pw;
+  int pre = 0;
+  for (int j = 0; j < K; ++j) {
+    const int n = vbhem::l4s_items(tot[j]);
+    if (first) first[j] = n ? vbhem::l4s_slot(pre, j, pw) : 0;
+    if (count) count[j] = n ? vbhem::l4s_slot(pre + n - 1, j, pw) - vbhem::l4s_slot(pre, j, pw) + 1 : 0;
+    pre += n;
+  }
+  return nitem;
+}

@@ -11,6 +11,7 @@
 
 #include "vbhem_estep.h"     // status codes
 #include "vbhem_switches.h"  // struct Switches, switches()
+#include "vbhem_list4_slots.h"
 
 namespace vbhem {
 
@@ -309,6 +310,15 @@ struct SplitArgs {
   double *pshift;                   // the shift, copied for the later kernels
   unsigned long long *ftag;
   unsigned long long ftag_val;
+  // fb_list4_kernel's statistics-accumulating variant (acc != 0; needs xinline): the
+  // gated sums Z nu_1, Z (A' o H) and (Z sum_t_nu) Us of the wave's items accumulated in
+  // its LDS and flushed as partials (vbhem_list4_slots.h) instead of the per-pair stores
+  // that stats_list_m_kernel read back
+  int acc;
+  int acc_nup;               // us_nup(NU) <= 16 kL4sMaxTiles
+  const double *accZ;        // [group][K] the pair weights (resp_kernel)
+  const double *accUs;       // the statistics copy of the prepared operand
+  double *acc_parts;         // l4s_max_slots partials of l4s_part_len doubles
 };
 
 // emission_prep_kernel's per-row arithmetic, one definition for it and for
@@ -404,12 +414,18 @@ hipError_t launch_bwd12(const SplitArgs &a, unsigned grid, hipStream_t st, hipEv
 // list mode (E, A, prior, Atg, logA, logPi, lists, nu1 / xi / tnu, flags)
 constexpr int kList4MaxK = 1024;
 bool list4_supported(int S, int SB, int T, int K);
-int list4_resident_blocks();  // per CU
+int list4_resident_blocks(bool acc = false);  // per CU (acc: the accumulating variant's)
 // the wavefronts of a grid of fb_list4_kernel when its per-wave queue of flagged pairs
 // (xinline) cannot overflow -- every cluster's list full -- else a count no inline
 // fallback accepts
 long long list4_inline_waves(const SplitArgs &a, unsigned grid);
 hipError_t launch_list4(const SplitArgs &a, unsigned grid, hipStream_t st);
+// the statistics-accumulating variant (SplitArgs::acc) takes the shape: NU within
+// kL4sMaxTiles feature tiles
+bool list4_acc_supported(int S, int SB, int T, int K, int NU);
+// its reduction (vbhem_stats.hip): per cluster the partials of its slots summed in slot
+// order, shifted back by z and written (a.assign) or added to slab 0's N1 | M | U sections
+hipError_t launch_list4_stats_reduce(const StatsArgs &a, const double *parts, int nw, hipStream_t st);
 
 // fb_list12_kernel (vbhem_fb_list12.hip): the gate-list pass for S = 12, SB <= 12, T = 10
 // (3 x 3 blocks of v_mfma_f64_4x4x4f64, the lattice in registers); fields as fb_list4_kernel

@@ -1210,8 +1210,9 @@ constexpr int kSuWaves = 4;
 
 // the prepared-operand statistics' output phase: the block's reduced sums in red
 // ([S][NU] | [S] | [S][S]) shifted back by z and written (or added) to slab c
+// (row >= 0: the entries of that state alone -- its moments, N1 entry and M row)
 __device__ __forceinline__ void su_output(const StatsArgs &p, const double *red, const double *zs,
-                                          int c, int nch, int j, int tid) {
+                                          int c, int nch, int j, int tid, int row = -1) {
   const int S = p.S, NU = p.NU, d = p.d;
   const bool full = p.covmode == kCovFull;
   const int KT = p.KT, tr = j / KT, jt = j - tr * KT;
@@ -1220,6 +1221,7 @@ __device__ __forceinline__ void su_output(const StatsArgs &p, const double *red,
   for (int o = tid; o < NO; o += 64 * kSuWaves) {
     double v;
     double *dst;
+    if (row >= 0 && (o < S * NU ? o / NU : o < S * NU + S ? o - S * NU : (o - S * NU - S) / S) != row) continue;
     if (o < S * NU) {
       const int s2 = o / NU, f = o - s2 * NU;
       const double *rs = red + (size_t)s2 * NU;
@@ -1591,6 +1593,69 @@ __global__ __launch_bounds__(64 * kSmWaves) void stats_list_m_kernel(const Stats
   su_output(p, red, zs, c, nch, j, tid);
 }
 
+// list4_stats_reduce_kernel: the gated sums that fb_list4_kernel's accumulating variant
+// left as partials (vbhem_list4_slots.h; U [S][NUP] | N1 [S] | M [S][S] per slot).  Block
+// (j, s) sums state s's row of cluster j -- its NU moments, its N1 entry and its M row,
+// at most 64 columns -- over the cluster's slots: 16 thread groups take a sixteenth of
+// the slots each, in slot order, eight loads in flight, and the sixteen sums are added
+// in group order (fixed: bit-reproducible).  su_output then shifts the row back by z
+// (which needs only the row's own sums) and writes or adds slab 0's sections; a cluster
+// with an empty list gets zeros.
+constexpr int kL4rParts = 16, kL4rCols = 64, kL4rThreads = kL4rParts * kL4rCols;
+__global__ __launch_bounds__(kL4rThreads) void list4_stats_reduce_kernel(const StatsArgs p,
+                                                                        const double *parts, int nw) {
+  extern __shared__ double lds[];
+  __shared__ int plan[2];
+  __shared__ double part[kL4rParts][kL4rCols];
+  const int tid = threadIdx.x, S = p.S, j = blockIdx.x / S, s2 = blockIdx.x - j * S;
+  const int NU = p.NU, NUP = us_nup(NU), d = p.d;
+  if (tid == 0) {
+    int nitem = 0, pre = 0;
+    for (int x = 0; x < p.K; ++x) {
+      if (x == j) pre = nitem;
+      nitem += l4s_items(p.list_tot[x]);
+    }
+    const int per = l4s_per_wave(nitem, nw), n = l4s_items(p.list_tot[j]);
+    plan[0] = l4s_slot(pre, j, per);
+    plan[1] = n ? l4s_slot(pre + n - 1, j, per) - plan[0] + 1 : 0;
+  }
+  __syncthreads();
+  const int s0 = plan[0], ns = plan[1];
+  const int NO = S * NU + S + S * S, PL = l4s_part_len(S, NUP);
+  double *red = lds;                                  // [S][NU] | [S] | [S][S]: row s2 filled
+  double *zs = red + NO;                              // [d]
+  for (int a = tid; a < d; a += kL4rThreads) zs[a] = p.uz[a];
+  // column col of the row: a moment, the N1 entry, an M entry -- in a partial, in red
+  const int q = tid / kL4rCols, col = tid - q * kL4rCols;
+  const bool cv = col < NU + 1 + S;
+  const int src = col < NU ? s2 * NUP + col : col == NU ? S * NUP + s2 : S * NUP + S + s2 * S + (col - NU - 1);
+  const int dst = col < NU ? s2 * NU + col : col == NU ? S * NU + s2 : S * NU + S + s2 * S + (col - NU - 1);
+  const int k0 = (int)((long long)ns * q / kL4rParts), k1 = (int)((long long)ns * (q + 1) / kL4rParts);
+  double acc = 0.0;
+  if (cv) {
+    const double *g = parts + (size_t)s0 * PL + src;
+    int k = k0;
+    for (; k + 7 < k1; k += 8) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = g[(size_t)(k + u) * PL];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc += v[u];
+    }
+    for (; k < k1; ++k) acc += g[(size_t)k * PL];
+  }
+  part[q][col] = acc;
+  __syncthreads();
+  if (q == 0 && cv) {
+    double t = part[0][col];
+#pragma unroll
+    for (int x = 1; x < kL4rParts; ++x) t += part[x][col];
+    red[dst] = t;
+  }
+  __syncthreads();
+  if (tid < 64 * kSuWaves) su_output(p, red, zs, 0, 1, j, tid, s2);
+}
+
 // stats_list_g_kernel<LG, SM>: stats_list_u_kernel for small moment vectors
 // (NU <= LG <= 32, e.g. d = 2 diag: NU = 5): a wavefront is 64 / LG lane groups, each
 // taking its own pair (group g of wave w: pairs w G + g, + 4 G, ...), so a pair
@@ -1939,6 +2004,16 @@ hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStre
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((stats_list_kernel<8>), grid, dim3(kSlThreads), lds, st, a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_list4_stats_reduce(const StatsArgs &a, const double *parts, int nw, hipStream_t st) {
+  if (!parts || nw < 1 || !a.uz || !a.list_tot) return hipErrorInvalidValue;
+  StatsArgs b = a;
+  b.nzero = 1;  // slab 0 alone holds the N1 | M | U sections
+  if (a.NU + 1 + a.S > kL4rCols) return hipErrorInvalidValue;  // a row's columns (NU <= 48, S = 8)
+  const size_t lds = ((size_t)(a.S * a.NU + a.S + a.S * a.S) + a.d) * sizeof(double);
+  hipLaunchKernelGGL(list4_stats_reduce_kernel, dim3(a.K * a.S), dim3(kL4rThreads), lds, st, b, parts, nw);
   return hipGetLastError();
 }
 

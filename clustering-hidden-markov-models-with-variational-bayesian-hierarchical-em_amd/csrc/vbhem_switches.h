@@ -20,6 +20,7 @@
   X(NO_LIST4, 0, "S = 8: fb_split_kernel's list mode instead of fb_list4_kernel")              \
   X(NO_LIST12, 0, "S = 12: fb_split_kernel's list mode instead of fb_list12_kernel")           \
   X(NO_K1_IN_KERNEL, 0, "short K1 through the emission GEMM, not inside the recursion")        \
+  X(NO_LIST4_STATS, 0, "S = 8: per-pair outputs + stats_list_m_kernel, not sums in fb_list4_kernel") \
   X(NO_LIST_INLINE, 0, "the gate-list pass's flagged pairs through an fb_exact_kernel launch") \
   X(NO_BWD2_PREP, 0, "emission_prep_kernel launched, not its work inside fb_bwd2_kernel")      \
   X(NO_FOLD_EXACT, 0, "the backward pass's fallback as a launch, not folded into resp_kernel") \

@@ -344,7 +344,10 @@ const char *vbhem_version(void);
 /* The kernel the calling thread's last E-step ran for a recursion pass, as the
  * kernel trace names it: pass 0 the every-pair pass (backward-only in the gated
  * schedule, K2-K4 in the dense one), pass 1 the gated schedule's gate-list pass;
- * "" before any such launch.  Benchmark labelling only (no reference
+ * 2: what summed the gated statistics of the last fused call's last base group,
+ * "vbhem::list4_stats_reduce_kernel" (the sums were accumulated in the gate-list
+ * pass) or "vbhem::stats_list_kernels";
+ * "" before any such launch. Benchmark labelling only (no reference
  * counterpart). */
 const char *vbhem_last_kernel(int pass);
 
