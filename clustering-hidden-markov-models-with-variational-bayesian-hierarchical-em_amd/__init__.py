@@ -8,7 +8,7 @@ from .h3m import (COV_DIAG, COV_FULL, CONFIGS, BaseSet, Posterior, baseem_draws,
                   baseem_init, clip_hyps, default_options, hmms_to_h3m_hem, synth_base_set,
                   synth_workload, weighted_kmeans, wtkmeans_init, wtkmeans_init_batch, wtkmeans_points,
                   wtkmeans_points_batched,
-                  gmm_mix_hier_em, gmmnew_init)
+                  gmm_mix_hier_em, gmm_mix_hier_em_batch, gmmnew_init, gmmnew_init_batch)
 from . import host  # noqa: F401
 
 __version__ = "0.1.0"

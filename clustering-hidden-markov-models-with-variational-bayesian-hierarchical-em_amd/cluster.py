@@ -20,7 +20,9 @@ weighted k-means of the base states' means, h3m.wtkmeans_init; MATLAB's kmeans
 replaced by a k-means++ stand-in; opt['init_engine'] = 'device' runs every trial's k-means
 in batched device calls, h3m.wtkmeans_init_batch, the default 'host' one trial after
 another in numpy), 'gmmNew' (vbhemhmm_init.m:103-293: the base
-Gaussians reduced by hierarchical EM, GMM_MixHierEM.m, h3m.gmmnew_init), or 'auto'
+Gaussians reduced by hierarchical EM, GMM_MixHierEM.m, h3m.gmmnew_init; with
+opt['init_engine'] = 'device' every trial's EM in one batched device call,
+h3m.gmmnew_init_batch), or 'auto'
 (vbhem_h3m_cluster.m:359-395: each of the three, the best bound wins).
 """
 from __future__ import annotations
@@ -34,7 +36,7 @@ from scipy.special import gammaln
 from . import em
 from .estep import EStepEngine
 from .h3m import (COV_FULL, BaseSet, baseem_draws, baseem_init, default_options, hmms_to_h3m_hem,
-                  hmms_to_h3m_hem_device, gmmnew_init, wtkmeans_init, wtkmeans_init_batch,
+                  hmms_to_h3m_hem_device, gmmnew_init, gmmnew_init_batch, wtkmeans_init, wtkmeans_init_batch,
                   wtkmeans_points)
 
 
@@ -83,13 +85,15 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     init_engine = opt.get("init_engine", "host")
     if init_engine not in ("host", "device"):
         raise ValueError(f"init_engine {init_engine!r}: 'host' or 'device'")
-    # init_engine='device': the k-means of every 'wtkmeans' trial in batched device calls
-    # (h3m.wtkmeans_init_batch); the other modes have no device path and run on the host
-    batched = init_engine == "device" and initmode == "wtkmeans"
+    # init_engine='device': the k-means of every 'wtkmeans' trial (h3m.wtkmeans_init_batch)
+    # and the hierarchical EM of every 'gmmNew' trial (h3m.gmmnew_init_batch) in batched
+    # device calls; 'baseem' has no device path and runs on the host
+    batched = init_engine == "device" and initmode in ("wtkmeans", "gmmNew")
     if batched:
-        posts = wtkmeans_init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
+        init_batch = wtkmeans_init_batch if initmode == "wtkmeans" else gmmnew_init_batch
+        posts = init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
     pts = wtkmeans_points(base, opt.get("initopt_mode", "r0")) if initmode == "wtkmeans" and not batched else None
-    if initmode == "gmmNew":
+    if initmode == "gmmNew" and not batched:
         bn = base.numpy()
         ns = bn["nstates"]
         pts = (np.concatenate([bn["centres"][i, :int(ns[i])] for i in range(base.N)]),

@@ -769,6 +769,14 @@ def gmmnew_init(base: BaseSet, opt: dict, seed: int, points=None) -> Posterior:
     Nv = opt["Nv"] * Kb
     _, cen, cov, _ = gmm_mix_hier_em(points[0], points[1], full, S, Nv,
                                      int(opt.get("initopt_iter", 30)), rng)
+    return _gmmnew_posterior(opt, mode, Kb, d, full, cen, cov, rng)
+
+
+def _gmmnew_posterior(opt: dict, mode: str, Kb: int, d: int, full: bool, cen, cov, rng) -> Posterior:
+    """The rest of 'gmmNew' after the reduced mixture (vbhemhmm_init.m:249-291): the draws
+    from ``rng`` in the reference's order, the counts and W.  ``opt`` is already clipped."""
+    K, S = opt["K"], opt["S"]
+    Nv = opt["Nv"] * Kb
     rng.random((K, S))                                   # (:249-250 the emissions' priors)
     pa = [make_a_prior(S, mode, rng) for _ in range(K)]
     omega = rng.random(K)
@@ -785,6 +793,153 @@ def gmmnew_init(base: BaseSet, opt: dict, seed: int, points=None) -> Posterior:
         W = 1.0 / ((v - d - 1)[:, :, None] * cov[None])
     return Posterior(alpha=opt["alpha0"] + Nsj, eta=eta, epsilon=eps, lam=lam, v=v, m=m, W=W,
                      W0mode="iid" if np.size(opt["W0"]) == 1 else "diag")
+
+
+# ----------------------------------------------------------------------------
+# 'gmmNew' for every trial in one batched device call (include/vbhem_init.h)
+# ----------------------------------------------------------------------------
+GHEM_OK, GHEM_DEGENERATE, GHEM_BAD, GHEM_NONFINITE, GHEM_SINGULAR = 0, 1, 2, 3, 4
+GHEM_MAX_DIM, GHEM_MAX_T = 16, 32
+
+
+class GhemDeviceEngine:
+    """vbhem_ghem_fit_batch of include/vbhem_init.h on one device."""
+
+    def __init__(self, device, chunk_trials=None):
+        self.dev = torch.device(device)
+        self.chunk = int(chunk_trials or 0)
+
+    def fit(self, X, C, full, T, virtual_samples, iterations, j0, u, init, want_logpost):
+        """X [n][d], C [n][d][d] | [n][d] numpy; j0 [R], u [R][max(T-1, 1)] numpy, or init
+        [R][T][d].  Returns dict(mxwt, centres, covars, logpost | None, logp, status, iters)
+        as numpy; only the rows of OK trials are meaningful."""
+        from . import _capi
+        lib, dev = _capi.lib(), self.dev
+        n, d = X.shape
+        R = len(init) if init is not None else len(j0)
+        cd = (d, d) if full else (d,)
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+        tx, tc = t(X, np.float64), t(C, np.float64)
+        tj = tu = ti = None
+        if init is not None:
+            ti = t(np.asarray(init, dtype=np.float64).reshape(R, T, d), np.float64)
+        else:
+            tj, tu = t(j0, np.int32), t(np.asarray(u, dtype=np.float64).reshape(R, max(T - 1, 1)), np.float64)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        mxwt, cen, cov, logp = z(R, T), z(R, T, d), z(R, T, *cd), z(R)
+        lpost = z(R, T, n) if want_logpost else None
+        status = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        iters = torch.zeros((R, 2), dtype=torch.int32, device=dev)
+        wb = lib.vbhem_ghem_workspace_bytes(n, d, int(full), T, R, self.chunk)
+        ws = _capi.workspace(wb, dev, 16)
+        p = _capi.ptr
+        _capi.check(lib.vbhem_ghem_fit_batch(n, d, int(full), T, R, p(tx), p(tc), float(virtual_samples),
+                                             int(iterations), p(tj), p(tu), p(ti), self.chunk, p(mxwt), p(cen),
+                                             p(cov), p(lpost), p(logp), p(status), p(iters), p(ws), ws.numel(),
+                                             _capi.stream(dev)), "vbhem_ghem_fit_batch")
+        return dict(mxwt=mxwt.cpu().numpy(), centres=cen.cpu().numpy(), covars=cov.cpu().numpy(),
+                    logpost=None if lpost is None else lpost.cpu().numpy(), logp=logp.cpu().numpy(),
+                    status=status.cpu().numpy(), iters=iters.cpu().numpy())
+
+
+def gmm_mix_hier_em_batch(centres: np.ndarray, covars: np.ndarray, full: bool, T: int, virtual_samples: float,
+                          iterations: int, seeds, device="cuda", chunk_trials=None, engine=None,
+                          init_centres=None, want_logpost: bool = False, info: Optional[dict] = None):
+    """``[gmm_mix_hier_em(centres, covars, full, T, virtual_samples, iterations,
+    Generator(PCG64(s))) for s in seeds]`` with the hierarchical EM of every trial in one
+    batched device call (csrc/vbhem_ghem.hip); the fourth entry of a trial's tuple is None
+    unless ``want_logpost``.  The host keeps the generators: per trial it skips the
+    discarded rand(T, n) (``bit_generator.advance(T * n)``: one 64-bit step per double),
+    draws kmeans_pp's first index and its T - 1 uniform draws, and leaves the generator
+    where gmm_mix_hier_em would (``info['rngs']``).  ``init_centres`` [R][T][d]: the start
+    centres of every trial, no seeding.  T = 1 is the closed form on the host.  A trial
+    whose status is not OK (a vanished D2 total, a logp that is not finite, a failed pivot,
+    non-finite points) is replayed through gmm_mix_hier_em with a fresh generator of its
+    seed and behaves as it does there.  ``engine``: a stand-in for
+    :class:`GhemDeviceEngine`; ``info`` also receives the seconds of the parts (fit: the
+    device call and its copies; host: the rest), the statuses, the iteration counts and
+    the replayed trials."""
+    import time
+    t0 = time.perf_counter()
+    X = np.ascontiguousarray(centres, dtype=float)
+    C = np.ascontiguousarray(covars, dtype=float)
+    n, d = X.shape
+    T = int(T)
+    for name, val, lim in (("d", d, GHEM_MAX_DIM), ("T", T, GHEM_MAX_T)):
+        if val > lim:
+            raise ValueError(f"gmm_mix_hier_em_batch: {name} = {val} exceeds the device limit {name} <= {lim}")
+    seeds = [int(s) for s in seeds]
+    R = len(seeds)
+    rngs = [np.random.Generator(np.random.PCG64(s)) for s in seeds]
+    inits = None if init_centres is None else np.asarray(init_centres, dtype=float).reshape(R, T, d)
+    fresh = lambda r: gmm_mix_hier_em(X, C, full, T, virtual_samples, iterations, rngs[r],
+                                      None if inits is None else inits[r])
+    if T == 1 or R == 0:
+        out = [fresh(r) for r in range(R)]
+        if info is not None:
+            info.update(rngs=rngs, replayed=[], fit=0.0, host=time.perf_counter() - t0)
+        return out
+    j0 = np.zeros(R, dtype=np.int64)
+    u = np.zeros((R, T - 1))
+    for r, g in enumerate(rngs):
+        g.bit_generator.advance(T * n)                   # (:91 post = rand(T, n): overwritten)
+        if inits is None:
+            j0[r] = g.integers(n)
+            u[r] = [g.random() for _ in range(T - 1)]
+    eng = engine if engine is not None else GhemDeviceEngine(device, chunk_trials)
+    t1 = time.perf_counter()
+    got = eng.fit(X, C, bool(full), T, float(virtual_samples), int(iterations), j0, u, inits, bool(want_logpost))
+    t2 = time.perf_counter()
+    out, replay = [], []
+    for r in range(R):
+        if got["status"][r] != GHEM_OK:
+            replay.append(r)
+            rngs[r] = np.random.Generator(np.random.PCG64(seeds[r]))
+            out.append(fresh(r))
+            continue
+        out.append((got["mxwt"][r], got["centres"][r], got["covars"][r],
+                    got["logpost"][r] if want_logpost else None))
+    if info is not None:
+        info.update(rngs=rngs, replayed=replay, status=got["status"], iters=got["iters"], logp=got["logp"],
+                    fit=t2 - t1)
+        info["host"] = time.perf_counter() - t0 - info["fit"]
+    return out
+
+
+def gmmnew_init_batch(base: BaseSet, opt: dict, seeds, device="cuda", chunk_trials=None, engine=None,
+                      info: Optional[dict] = None) -> List[Posterior]:
+    """``[gmmnew_init(base, opt, s) for s in seeds]`` with the hierarchical EM of every
+    trial in one batched device call (:func:`gmm_mix_hier_em_batch`); the draws after the
+    EM come from the trial's generator as gmmnew_init takes them.  ``info`` receives the
+    seconds of the parts (points, fit, host: the rest), the replayed trials and the E-steps
+    every device trial evaluated."""
+    import time
+    t0 = time.perf_counter()
+    copt = clip_hyps(opt)
+    mode = copt.get("initopt_mode", "r0")
+    if "m" in mode:
+        raise ValueError("initopt.mode 'm' (priors from the base HMMs) is not supported for gmmNew")
+    S = int(copt["S"])
+    Kb, d = base.N, base.d
+    full = base.covmode == COV_FULL
+    for name, val, lim in (("d", d, GHEM_MAX_DIM), ("S", S, GHEM_MAX_T)):
+        if val > lim:
+            raise ValueError(f"gmmnew_init_batch: {name} = {val} exceeds the device limit {name} <= {lim}")
+    bn = base.numpy()
+    ns = bn["nstates"]
+    X = np.concatenate([bn["centres"][i, :int(ns[i])] for i in range(Kb)])
+    C = np.concatenate([bn["covars"][i, :int(ns[i])] for i in range(Kb)])
+    t1 = time.perf_counter()
+    sub = {}
+    fits = gmm_mix_hier_em_batch(X, C, full, S, copt["Nv"] * Kb, int(copt.get("initopt_iter", 30)), seeds, device,
+                                 chunk_trials, engine, info=sub)
+    posts = [_gmmnew_posterior(copt, mode, Kb, d, full, cen, cov, g) for (_, cen, cov, _), g in zip(fits, sub["rngs"])]
+    if info is not None:
+        total = time.perf_counter() - t0
+        info.update(points=t1 - t0, fit=sub["fit"], replayed=sub["replayed"],
+                    esteps=[int(v) for v in sub["iters"][:, 1]] if "iters" in sub else [])
+        info["host"] = total - info["points"] - info["fit"]
+    return posts
 
 
 # ----------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 /*
- * vbhem_init.h -- C-ABI of the batched 'wtkmeans' initialisation on MI355X
+ * vbhem_init.h -- C-ABI of the batched clustering initialisations on MI355X: 'wtkmeans'
+ * here, 'gmmNew' (vbhem_ghem_fit_batch) further down.  The batched 'wtkmeans' initialisation
  * (vbhemhmm_init.m:294-425 as h3m.py wtkmeans_init restates it): the k-means++ seeding with
  * Lloyd updates (h3m.kmeans_pp) and the weighted k-means (my_weighted_kmeans.m,
  * h3m.weighted_kmeans) of every TRIAL of a list in two calls.  Every random draw is an
@@ -66,6 +67,47 @@ int vbhem_wtk_states_batch(int n, int d, int K, int S, int R, const double *x_de
                            const long long *off_dev, long long total_members, const int *j0_dev,
                            const double *u_dev, double *centres_dev, int *status_dev, int *iters_dev,
                            void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/*
+ * The batched 'gmmNew' initialisation (vbhemhmm_init.m:103-293, GMM_MixHierEM.m as
+ * h3m.gmm_mix_hier_em restates it for T >= 2): the mixture of all n base-state Gaussians
+ * reduced to T components by hierarchical EM, every TRIAL of a list in one call.  A trial
+ * is its k-means++ draws (j0, u: as above, over all n points) or, with init_centres given,
+ * its start centres (no seeding, no draws read).
+ *
+ * Layouts (row-major, DEVICE pointers):
+ *   points:  x[n][d]; cov[n][d][d] (full != 0) or cov[n][d]
+ *   draws:   j0[R], u[R][max(T - 1, 1)]; init_centres[R][T][d] or NULL
+ *   outputs: mxwt[R][T], centres[R][T][d], covars[R][T][d][d] or [R][T][d], logpost[R][T][n]
+ *            or NULL (not wanted), logp[R] (of the last E-step evaluated), status[R],
+ *            iters[R][2] (Lloyd passes of the seeding, E-steps evaluated)
+ * Status: VBHEM_WTK_OK, VBHEM_WTK_DEGENERATE (the seeding's D2 total is zero),
+ * VBHEM_WTK_BAD (a non-finite coordinate or covariance entry, a draw out of range),
+ * VBHEM_GHEM_NONFINITE (a logp that is not finite), VBHEM_GHEM_SINGULAR (a pivot of a
+ * covariance's Cholesky factor that is not > 0).  A trial that is not OK writes its status
+ * alone.
+ * Limits: d <= 16, 2 <= T <= 32; beyond: VBHEM_ERR_UNSUPPORTED (T < 2: VBHEM_ERR_ARG).
+ *
+ * Every n-term sum runs over point tiles whose size depends on (n, d) only, and the tile
+ * partials are added in tile order: a trial's result depends on its own inputs only -- not
+ * on R, its place in the list or chunk_trials (trials per round of launches; 0: as many as
+ * fit VBHEM_GHEM_DEFAULT_WORKSPACE bytes).
+ */
+#define VBHEM_GHEM_NONFINITE 3
+#define VBHEM_GHEM_SINGULAR 4
+
+#define VBHEM_GHEM_MAX_DIM 16
+#define VBHEM_GHEM_MAX_T 32
+#define VBHEM_GHEM_DEFAULT_WORKSPACE ((size_t)1 << 30)
+
+/* Workspace of a call (0 on invalid / unsupported sizes). */
+size_t vbhem_ghem_workspace_bytes(int n, int d, int full, int T, int R, int chunk_trials);
+
+int vbhem_ghem_fit_batch(int n, int d, int full, int T, int R, const double *x_dev, const double *cov_dev,
+                         double virtual_samples, int iterations, const int *j0_dev, const double *u_dev,
+                         const double *init_centres_dev, int chunk_trials, double *mxwt_dev, double *centres_dev,
+                         double *covars_dev, double *logpost_dev, double *logp_dev, int *status_dev, int *iters_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
