@@ -212,6 +212,9 @@ EXPORTS = {
     "vbhmm_ccfd_rho": (_c_int, [_vp, _c_int, ctypes.POINTER(ctypes.c_double), _c_int, _vp, _vp]),
     "vbhmm_ccfd_delta": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _vp, _vp, _vp]),
     "vbhmm_ccfd_border": (_c_int, [_vp, _c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "vbhmm_kld_jobs_workspace_bytes": (_c_size, [_c_int, _vp, _c_int, _vp]),
+    "vbhmm_kld_jobs": (_c_int, [ctypes.POINTER(ScoreHmmsT), _vp, ctypes.POINTER(SeqsT), _c_int, _vp, _vp, _c_int,
+                                _vp, _vp, _c_size, _vp, _vp]),
     "vbhmm_dic_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int]),
     "vbhmm_dic_loglik": (_c_int, [ctypes.POINTER(BaseT), ctypes.POINTER(DicModelsT), _c_int, _vp, _vp,
                                   _vp, _c_size, _vp]),

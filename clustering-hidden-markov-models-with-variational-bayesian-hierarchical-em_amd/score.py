@@ -247,6 +247,40 @@ def kld_matrix(hmms, data_by_hmm, normalize: bool = True, device="cuda") -> torc
     return _segment_mean(own[None, :] - ll, counts).T.contiguous()
 
 
+def kld_jobs(hset: HmmSet, batch, lists, jobs) -> torch.Tensor:
+    """Many vbhmm_kld values in one fused call (include/vbhmm_kld.h), ``[P]`` fp64 on the
+    device: for job p = ``jobs[p]`` = (a, b, list),
+    ``kl[p] = mean over n in lists[list] of (ll_a(n) / T_n - ll_b(n) / T_n)``.
+    ``lists``: a list of int sequences, indices into ``batch`` (sequences or a
+    :class:`SequenceBatch`) in any order, repeats allowed; ``jobs``: ``[P][3]`` ints.  An
+    empty list or an empty sequence in it gives NaN.  No ``[H][N]`` matrix is built:
+    work and memory follow the sum of the jobs' list lengths.  An index out of range
+    raises :class:`_capi.VbhemError` naming it, before anything runs on the device."""
+    sb = _batch(hset, batch)
+    jb = np.ascontiguousarray(np.asarray(jobs, dtype=np.int64).reshape(-1, 3))
+    ls = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+    flat = np.concatenate(ls) if ls else np.zeros(0, dtype=np.int64)
+    for a in (jb, flat):
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("kld_jobs: an index does not fit 32 bits")
+    jb, items = jb.astype(np.int32), np.ascontiguousarray(flat.astype(np.int32))
+    off = np.zeros(len(ls) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(l) for l in ls])
+    P = int(jb.shape[0])
+    out = torch.empty((P,), dtype=F64, device=hset.device)
+    lib = hset.lib
+    nb = int(lib.vbhmm_kld_jobs_workspace_bytes(len(ls), off.ctypes.data, P, jb.ctypes.data))
+    ws = _capi.workspace(nb, hset.device, align=16)
+    sd = sb.desc()
+    with torch.cuda.device(hset.device):
+        _capi.check(lib.vbhmm_kld_jobs(ctypes.byref(hset.desc()), _capi.ptr(hset.prepared), ctypes.byref(sd),
+                                       len(ls), off.ctypes.data, items.ctypes.data if items.size else None, P,
+                                       jb.ctypes.data, _capi.ptr(ws), ws.numel(), _capi.ptr(out),
+                                       hset._stream()),
+                    "vbhmm_kld_jobs")
+    return out
+
+
 # ----------------------------------------------------------------------------
 # reference-named wrappers (host data in and out)
 # ----------------------------------------------------------------------------
