@@ -97,6 +97,31 @@ SHAPES = [
 ]
 
 
+# the state counts S <= 16 that SHAPES leaves out: 7, 9, 10, 11, 13, 14, 15 (same tuple layout;
+# tests/test_fb_state_counts_gpu.py).  fb_split_kernel holds rows in LPC lanes of SH =
+# ceil(S / LPC) rows each (dense / list: LPC = 2 at S = 7, 4 from 9; backward: 1, 2), so
+# these S have padded rows (S = 9: lane h = 3 holds none but padded rows) and 14 to 60
+# lanes per pair: pairs straddle wavefronts and the block's last lanes idle.
+# fb_bwd2_kernel has a padded second column at S = 7 and, from 9, 64 % S idle lanes per
+# wave with pairs across its 16-lane DPP rows.  N = 37 (75 at S = 7): with every pair
+# gated a cluster's list is more than two of the list kernel's work items (at most
+# 512 / (S LPC) pairs) and fb_bwd2_kernel's last tile ends inside a wave
+STATE_COUNT_SHAPES = [
+    ("S7_ragged", 9, 3, 7, 7, 2, 1, 10, True),    # d = 2 full: K1 inside the kernels
+    ("S7_sb4", 6, 4, 7, 4, 3, 1, 6, False),       # emission GEMM path, padded base columns
+    ("S7_lists", 75, 2, 7, 7, 2, 0, 10, False),
+    ("S9_ragged", 9, 3, 9, 9, 3, 1, 10, True),
+    ("S9_sb5", 5, 2, 9, 5, 2, 0, 6, False),
+    ("S9_lists", 37, 4, 9, 9, 2, 0, 10, False),
+    ("S10_lists", 37, 3, 10, 10, 2, 1, 10, False),
+    ("S11_ragged", 37, 3, 11, 8, 4, 0, 7, True),
+    ("S13_ragged", 37, 3, 13, 13, 3, 1, 10, True),
+    ("S13_sb1", 4, 2, 13, 1, 2, 1, 5, False),
+    ("S14_sb9", 37, 2, 14, 9, 2, 0, 6, False),
+    ("S15_ragged", 37, 3, 15, 15, 4, 1, 10, True),
+]
+
+
 def make_reduced(K=3, S=3, d=2, covmode=1, seed=0, zero_transition=False) -> dict:
     """Point-estimate reduced HMMs for the VHEM sibling (hem_hmm_bwd_fwd_mex.c):
     Dirichlet rows for A and prior, means in [0, 5]^d, SPD covariances

@@ -65,10 +65,11 @@ def fused_mode(request):
     _capi.set_fused_mode(prev)
 
 
-@pytest.fixture(params=[("gated", 100.0), ("dense", 100.0), ("gated", 1e-9)],
-                ids=["gated-Nv100", "dense-Nv100", "gated-allgated"])
+@pytest.fixture(params=[("gated", 100.0), ("dense", 100.0), ("gated", 1e-9), ("gated", 0.3)],
+                ids=["gated-Nv100", "dense-Nv100", "gated-allgated", "gated-allpass"])
 def mode_tscale(request):
-    """(schedule, tscale): the all-gated edge case targets the gated schedule only."""
+    """(schedule, tscale): the all-gated and all-pass edge cases target the gated schedule
+    only."""
     from vbhem_amd import _capi
     mode, tscale = request.param
     prev = _capi.set_fused_mode(_capi.FUSED_GATED if mode == "gated" else _capi.FUSED_DENSE)
@@ -76,17 +77,30 @@ def mode_tscale(request):
     _capi.set_fused_mode(prev)
 
 
+# the all-pass regime's tscale where 0.3 leaves some Z below the 1e-8 gate (high d or long
+# T: L_elbo differs by hundreds between clusters, and Z = hat_Z tilde N shrinks with tscale)
+ALLPASS_TSCALE = {"C2like": 0.03, "C4like": 0.03, "C5like": 0.003, "d16diag": 0.03, "d20": 0.03}
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=[s[0] for s in SHAPES])
 def test_fused_matches_oracle(vb, vo, shape, mode_tscale):
     """tscale = Nv: 100 (the configs' virtual samples: Z mostly one-hot, the gate
-    drops most pairs) and 1e-9 (every Z < 1e-8: no pair passes the gate)."""
+    drops most pairs), 1e-9 (every Z < 1e-8: no pair passes the gate) and 0.3
+    (ALLPASS_TSCALE for some shapes; Z soft: every pair of every cluster passes the gate,
+    checked on the oracle, so every cluster's list is full)."""
     name, N, K, S, Sb, d, cov, T, ragged = shape
     tscale = mode_tscale
+    allpass = tscale == 0.3
+    if allpass:
+        tscale = ALLPASS_TSCALE.get(name, 0.3)
     cs = make_case(N, K, S, Sb, d, cov, seed=seed_of(name) + 1, ragged=ragged, tau=T)
     base, consts = cs["base"], cs["consts"]
     pairs = vo.c_estep_pairs(base, consts, T, nthreads=4)
     tN = tscale * N * base["omega"]
     logOmega, hz, Z, Nj = vo.responsibilities(pairs["LL_elbo"], tN, cs["post"]["alpha"])
+    if allpass:
+        Z100 = vo.responsibilities(pairs["LL_elbo"], 100.0 * N * base["omega"], cs["post"]["alpha"])[2]
+        assert (Z > 1e-8).all() and (Z > 1e-8).sum() > (Z100 > 1e-8).sum()
     st = vo.c_statistics(Z, pairs, cov)
     eng = engine(vb, base, consts, T)
     eng.set_log_omega(logOmega)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 from scipy.special import logsumexp
 
-from cases import SHAPES, make_case
+from cases import SHAPES, STATE_COUNT_SHAPES, make_case
 from conftest import rel_err
 
 PAIR_KEYS = ("LL_elbo", "sum_nu_1", "sum_xi", "emit_pr", "emit_mu", "emit_Mu")
@@ -32,7 +32,8 @@ def emission_E(base, consts, i, j):
     return -0.5 * (d * np.log(2 * np.pi) + c[None, :] + tr + mah)
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=[s[0] for s in SHAPES])
+@pytest.mark.parametrize("shape", SHAPES + STATE_COUNT_SHAPES,
+                         ids=[s[0] for s in SHAPES + STATE_COUNT_SHAPES])
 def test_c_oracle_matches_numpy_twin(vo, shape):
     name, N, K, S, Sb, d, cov, T, ragged = shape
     cs = make_case(N, K, S, Sb, d, cov, seed=zlib.crc32(name.encode()) % 1000, ragged=ragged, tau=T)

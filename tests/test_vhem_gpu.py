@@ -43,6 +43,13 @@ CASES = {
     # Sb > S: fb_pairs_kernel (generic path, dense statistics)
     "pairs_K3": (2, 5, 2, 1, False, 4, 3, 2.5, "nt"),
     "pairs_K16": (2, 5, 2, 1, False, 4, 16, 1.0, ""),
+    # state counts with padded rows in fb_split_kernel: the first pass's backward mode at
+    # S = 7 (one lane per column), 9 and 13 (two lanes, odd S), the list pass on four lanes
+    # at S = 9 (the last lane's rows all padded) and 13 (the names sort last: the seeds of
+    # the cases above stay what they were)
+    "split_S7": (7, 7, 2, 1, True, 10, 3, 2.5, "nt"),
+    "split_S9": (9, 9, 3, 1, True, 10, 4, 1.0, "t"),
+    "split_S13": (13, 11, 2, 0, False, 7, 3, 2.5, ""),
 }
 NV = 100
 
@@ -164,6 +171,13 @@ def test_fused_vhem_matches_restatement(vb, vo, schedule, name):
         assert (off == 0).any() and (off > 0).any()
     eng = gpu_engine(vb, base, K, S, T)
     vec, Z = run_fused(vb, eng, base, h, opt)
+    if name.startswith("split_") and schedule == "gated":
+        # the instances these cases are here for: fb_split_kernel<S, LPC, mode>, backward
+        # (1) then list (2) mode
+        from vbhem_amd import _capi
+        assert (_capi.last_kernel(0), _capi.last_kernel(1)) == (
+            "vbhem::fb_split_kernel<%d, %d, 1>" % (S, 1 if S <= 8 else 2),
+            "vbhem::fb_split_kernel<%d, %d, 2>" % (S, 2 if S <= 8 else 4))
     check_fused(vb, name, vec, Z)
 
 
