@@ -1,0 +1,37 @@
+// vbhem_estep_sched.h -- what the C ABI (vbhem_capi.hip) calls of the E-step's
+// scheduler (vbhem_estep_sched.hip): workspace sizes and the two calls' schedules,
+// entered after the argument checks.
+#pragma once
+#include <cstddef>
+
+#include "vbhem_estep.h"
+
+namespace vbhem {
+
+// bytes of workspace (need_tnu: sum_t_nu is not an output and lives in the workspace)
+size_t pairs_workspace_bytes(const vbhem_base_t *b, const vbhem_cluster_t *c, int T, bool need_tnu);
+size_t fused_workspace_bytes(const vbhem_base_t *b, const vbhem_cluster_t *c, int T, int R);
+
+// vbhem_estep_pairs / vhem_estep_pairs (smooth) on checked arguments, N > 0
+int sched_estep_pairs(const vbhem_base_t *base, const vbhem_cluster_t *clus, int T, double smooth,
+                      double *LL_elbo_dev, double *sum_nu_1_dev, double *emit_pr_dev,
+                      double *emit_mu_dev, double *emit_Mu_dev, double *sum_xi_dev,
+                      double *sum_t_nu_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+// the VHEM mode of the fused call (vhem_estep_fused*): null for VBHEM
+struct VhemIn {
+  double smooth, inf_norm;
+  const double *omegaB;
+};
+// vbhem_estep_fused_trials / vhem_estep_fused_trials on checked arguments; done_word
+// (optional): the completion word armed for this call (vbhem_arm_done_word)
+int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int R, int T,
+                      const double *tildeN_dev, const double *logOmega_dev, double *stats_dev,
+                      double *hatZ_dev, double *LL_elbo_dev, void *workspace_dev,
+                      size_t workspace_bytes, void *stream, const VhemIn *vh,
+                      unsigned long long *done_word, unsigned long long done_val);
+
+// vbhem_last_kernel
+const char *last_kernel(int pass);
+
+}  // namespace vbhem

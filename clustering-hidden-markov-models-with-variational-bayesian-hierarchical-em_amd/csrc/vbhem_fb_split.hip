@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "vbhem_internal.h"
+#include "vbhem_estep_plan.h"  // SplitLPC, BwdLPC, SplitLayout
 #include "vbhem_exact.h"
 #include "vbhem_log_table.h"
 #include "vbhem_math.h"
@@ -789,17 +790,5 @@ hipError_t launch_split(const SplitArgs &a, unsigned grid, size_t lds, hipStream
     default: return hipErrorInvalidValue;
   }
 }
-
-bool split_supported(int S, int SB, int d) {
-  return S >= 1 && S <= kSplitMaxS && SB >= 1 && SB <= S && d >= 1 && d <= 64;
-}
-
-int split_lpc(int S) {
-#ifdef VBHEM_SPLIT_LPC5
-  if (S == 5) return VBHEM_SPLIT_LPC5;
-#endif
-  return S <= 4 ? 1 : S <= 8 ? 2 : 4;
-}
-int split_lpc_bwd(int S) { return S <= 8 ? 1 : 2; }
 
 }  // namespace vbhem

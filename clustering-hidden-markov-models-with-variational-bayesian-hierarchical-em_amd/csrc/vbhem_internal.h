@@ -15,8 +15,12 @@
 
 namespace vbhem {
 
-// record `msg` for vbhem_last_error() and return `code` (vbhem_capi.hip)
+// record `msg` for vbhem_last_error() and return `code` (vbhem_capi.hip); a refused
+// launch's pending HIP error is consumed with it
 int set_error(int code, const std::string &msg);
+// the descriptors' sizes, covmode and (need_ptrs) input arrays of an E-step call
+// (vbhem_capi.hip): VBHEM_OK, or the error recorded
+int check_inputs(const vbhem_base_t *b, const vbhem_cluster_t *c, int T, bool need_ptrs = true);
 // VBHEM_ERR_HIP with the message "<where>: <HIP's text for e>"
 static inline int hip_fail(hipError_t e, const char *where) {
   return set_error(VBHEM_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e));
@@ -152,27 +156,7 @@ struct StatsArgs {
 
 // fb_split_kernel (one base-state column per LPC lanes; S <= kSplitMaxS, SB <= S).
 constexpr int kSplitMaxS = 16;
-template <int S>
-struct SplitLPC {
-#ifdef VBHEM_SPLIT_LPC5   // A/B: lanes per column of the dense / list modes at S = 5
-  static constexpr int value = S <= 4 ? 1 : S == 5 ? VBHEM_SPLIT_LPC5 : S <= 8 ? 2 : 4;
-#else
-  static constexpr int value = S <= 4 ? 1 : S <= 8 ? 2 : 4;
-#endif
-};
-// the backward-only mode's alternative (no H / sum_t_nu registers: wider columns fit)
-template <int S>
-struct BwdLPC {
-  static constexpr int value = S <= 8 ? 1 : 2;
-};
-template <int S, int LPC>
-struct SplitLayout {
-  static constexpr int SH = (S + LPC - 1) / LPC;           // rows per lane
-  static constexpr int XCS = (LPC * SH + 1) / 2 * 2 + 2;   // slab column stride (even)
-  static constexpr int XP = S * XCS + 2;                    // per-pair slab
-  static constexpr int HEAD = 2 * S * S + 2 * S;            // At, AtT, amax, lpi
-  static constexpr int OFF_X = (HEAD + 1) / 2 * 2;
-};
+// (its lanes per column and LDS layout: SplitLPC, BwdLPC, SplitLayout in vbhem_estep_plan.h)
 // K1 emission GEMM (vbhem_emission.hip)
 // W' / bias' padding of the emission GEMM: k-rows to a multiple of 4 (MFMA k-step),
 // rows (j, s) to a multiple of 128 (a chunk of 8 MFMA row tiles)
@@ -366,9 +350,6 @@ __device__ __forceinline__ double k1_entry(const SplitArgs &p, int jr,
     if (e < p.ekdp) acc = fma(p.eW[(size_t)e * p.eksp + jr], u[e], acc);
   return acc;
 }
-bool split_supported(int S, int SB, int d);
-int split_lpc(int S);      // lanes per column
-int split_lpc_bwd(int S);  // lanes per column, alternative for kFbBackward (BwdLPC)
 hipError_t launch_split(const SplitArgs &a, unsigned grid, size_t lds, hipStream_t st);
 int split_resident_blocks(const SplitArgs &a, size_t lds);  // per CU, for a.mode
 
@@ -386,9 +367,18 @@ int bwd2_resident_blocks(int S, int nwb, size_t lds);
 hipError_t launch_bwd2(const SplitArgs &a, unsigned grid, size_t lds, hipStream_t st,
                        hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
-// kernel timing hooks for code outside vbhem_capi.hip (null when timing is off)
+// kernel timing (vbhem_timing.hip): hooks for the launching code, null / no-ops when
+// timing is off for this thread, this launch (level 2: fb launches only) or a stream
+// that is being captured
 void *timing_begin(hipStream_t st);
 void timing_end_em_math(void *ev0, hipStream_t st);
+enum TimingSpan : int { kTimeFb = 0, kTimeStats, kTimeEmission, kTimeGatedForward, kTimeEmMath };
+// a pool event recorded on st, null when off; with `end`: that event and a second one in
+// *end, neither recorded (the dispatch itself records them at the kernel's start and end)
+hipEvent_t timing_start(hipStream_t st, bool fb_launch = false, hipEvent_t *end = nullptr);
+// closes the span opened by ev0 (null: nothing) with ev1, or an event recorded on st now
+void timing_stop(TimingSpan span, hipEvent_t ev0, hipStream_t st, hipEvent_t ev1 = nullptr,
+                 long long fb_pairs = 0);
 
 // fb_bwd4_kernel (vbhem_fb_bwd4.hip): the backward-only pass for S = 8, SB <= 8 with
 // both contractions on v_mfma_f64_4x4x4f64; SplitArgs fields as fb_bwd2_kernel

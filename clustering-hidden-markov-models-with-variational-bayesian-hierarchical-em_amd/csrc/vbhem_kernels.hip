@@ -474,7 +474,7 @@ hipError_t launch_fb(const FbArgs &a, dim3 grid, dim3 block, size_t lds, hipStre
 
 hipError_t launch_fb_exact(const FbArgs &a, double *scratch, size_t stride, int nslots,
                            hipStream_t st, bool from_fold) {
-  // the scratch holds kExactSlots slots, one per wavefront (vbhem_capi.hip)
+  // the scratch holds kExactSlots slots, one per wavefront (vbhem_estep_sched.hip)
   if (nslots != kExactSlots) return hipErrorInvalidValue;
   const size_t lds = exact_wave_in_lds(a.S, a.SB)
                          ? (size_t)(kExactBlock / 64) * exact_wave_lds(a.S, a.SB) * sizeof(double)
