@@ -24,6 +24,10 @@ Gaussians reduced by hierarchical EM, GMM_MixHierEM.m, h3m.gmmnew_init; with
 opt['init_engine'] = 'device' every trial's EM in one batched device call,
 h3m.gmmnew_init_batch), or 'auto'
 (vbhem_h3m_cluster.m:359-395: each of the three, the best bound wins).
+
+The EM of the trials (opt['em_engine']): 'host' (the default) batches the E-step and
+runs the rest of an iteration in numpy, trial by trial; 'device' keeps the whole loop
+of a chunk of trials on the GPU (native_em.run_trials).
 """
 from __future__ import annotations
 
@@ -89,6 +93,11 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     # and the hierarchical EM of every 'gmmNew' trial (h3m.gmmnew_init_batch) in batched
     # device calls; 'baseem' has no device path and runs on the host
     batched = init_engine == "device" and initmode in ("wtkmeans", "gmmNew")
+    # em_engine='device': the EM of every chunk of trials stays on the device
+    # (native_em.run_trials); the default 'host' runs its per-iteration math in numpy
+    em_engine = opt.get("em_engine", "host")
+    if em_engine not in ("host", "device"):
+        raise ValueError(f"em_engine {em_engine!r}: 'host' or 'device'")
     if batched:
         init_batch = wtkmeans_init_batch if initmode == "wtkmeans" else gmmnew_init_batch
         posts = init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
@@ -112,7 +121,10 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
         for r0 in range(0, R, per):
             chunk = posts[r0:r0 + per]
             eng = make(base, len(chunk) * K, S, opt["tau"], trials=len(chunk))
-            tr = em.vbhem_h3m_c_trials(chunk, eng, opt)
+            # (d > 16 has no device-side EM math: the host engine, as the trial-by-trial
+            # path below for the shapes without a batched E-step)
+            on_dev = em_engine == "device" and base.d <= 16
+            tr = em.vbhem_h3m_c_trials(chunk, eng, opt, **(dict(em_engine="device") if on_dev else {}))
             results.extend(tr.results)
             LLs.extend(tr.LLall.tolist())
             del eng

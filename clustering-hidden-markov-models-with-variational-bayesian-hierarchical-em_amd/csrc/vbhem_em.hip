@@ -24,6 +24,7 @@
 
 #include "vbhem_em.h"
 #include "vbhem_em_dev.h"
+#include "vbhem_em_trial_ctrl.h"
 #include "vbhem_internal.h"
 #include "vbhem_special.h"
 
@@ -684,6 +685,70 @@ int em_run_host(const vbhem_base_t *base, const double *tildeN_dev, int T, const
   return VBHEM_OK;
 }
 
+// Mapped host memory of the trials loop (its words and the bounds of every trial):
+// a per-device pool like g_mapped_free, of blocks that only grow.
+struct MappedBuf {
+  char *h = nullptr, *d = nullptr;
+  size_t bytes = 0;
+};
+std::map<int, std::vector<MappedBuf>> g_mapped_bufs;
+
+hipError_t acquire_mapped_buf(size_t bytes, MappedBuf &m) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  {
+    std::lock_guard<std::mutex> g(g_mapped_mu);
+    auto &v = g_mapped_bufs[dev];
+    for (size_t x = 0; x < v.size(); ++x)
+      if (v[x].bytes >= bytes) {
+        m = v[x];
+        v.erase(v.begin() + (long)x);
+        return hipSuccess;
+      }
+    if (!v.empty()) {  // too small: replaced by the larger one
+      (void)hipHostFree(v.back().h);
+      v.pop_back();
+    }
+  }
+  m.bytes = (bytes + 4095) / 4096 * 4096;
+  e = hipHostMalloc(reinterpret_cast<void **>(&m.h), m.bytes, hipHostMallocMapped);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d), m.h, 0);
+  return e;
+}
+
+void release_mapped_buf(const MappedBuf &m) {
+  if (!m.h) return;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return;
+  std::lock_guard<std::mutex> g(g_mapped_mu);
+  g_mapped_bufs[dev].push_back(m);
+}
+
+size_t post_len(int K, int S, int d, size_t dd) {
+  return (size_t)K + 3 * (size_t)K * S + (size_t)K * S * S + (size_t)K * S * d + (size_t)K * S * dd;
+}
+
+// the doubles of vbhem_em_run_trials' workspace after the E-step's own
+size_t trials_ws_doubles(int N, int K, int S, int d, size_t dd, int R, size_t slen) {
+  const size_t KS = (size_t)K * S;
+  const size_t consts = KS * S + KS + KS * d + KS * dd + KS + (size_t)K;
+  return (size_t)R * (2 * consts + 2 * post_len(K, S, d, dd) + 2 * KS + KS * 13 + 2 * slen +
+                      2 * (size_t)N * K) +
+         (size_t)d + (size_t)d * d + ((size_t)R * sizeof(vbhem::TrialCtrl) + 7) / 8 +
+         ((size_t)R * sizeof(int) + 7) / 8;
+}
+
+// why a shape is outside vbhem_em_run_trials (nullptr: supported)
+const char *trials_unsupported(const vbhem_base_t *base, int K, int S, int R) {
+  if (R < 1 || K < 1 || S < 1) return "R, KT and S must be positive";
+  if ((long long)R * K > 256) return "R * KT > 256 (vbhem_estep_fused_trials)";
+  if (S > 16) return "S > 16 (vbhem_estep_fused_trials)";
+  if (base->SB > S) return "Sb > S (vbhem_estep_fused_trials)";
+  if (!vbhem::em_dev_supported(base->d, S)) return "d > 16 (the device-side EM math)";
+  return nullptr;
+}
+
 }  // namespace
 
 int vbhem_em_run_ext(const vbhem_base_t *base, const double *tildeN_dev, int T,
@@ -843,6 +908,186 @@ int vbhem_em_run(const vbhem_base_t *base, const double *tildeN_dev, int T,
   return vbhem_em_run_ext(base, tildeN_dev, T, opt, post, LogLs, iters, L_final, stable, stats_dev,
                           hatZ_dev, LL_dev, workspace_dev, workspace_bytes, stream, allreduce,
                           allreduce_ctx, nullptr);
+}
+
+size_t vbhem_em_trials_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T) {
+  if (!base || trials_unsupported(base, KT, S, R)) return 0;
+  const int d = base->d;
+  const size_t dd = base->covmode == VBHEM_COV_FULL ? (size_t)d * d : (size_t)d;
+  vbhem_cluster_t c = {R * KT, S, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const size_t fused = vbhem_fused_trials_workspace_bytes(base, &c, R, T);
+  if (fused == 0) return 0;
+  const size_t slen = vbhem_stats_len(KT, S, d, base->covmode);
+  return (fused + 255) / 256 * 256 +
+         trials_ws_doubles(base->N, KT, S, d, dd, R, slen) * sizeof(double) + 256;
+}
+
+int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
+                        const vbhem_em_opt_t *opt, vbhem_post_t *posts, double *LogLs, int *iters,
+                        double *L_final, int *stable, double *stats_out, double *hatZ_dev,
+                        double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  if (!base || !posts || R < 1 || !post_ok(&posts[0]) || !opt_ok(opt, posts[0].d) || !LogLs ||
+      !iters || !L_final || !stable || !stats_out || !hatZ_dev || !LL_dev || !tildeN_dev)
+    return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: null or invalid argument");
+  const int K = posts[0].K, S = posts[0].S, d = posts[0].d, cov = posts[0].covmode;
+  if (d != base->d || cov != base->covmode)
+    return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: d / covmode differ from the base set's");
+  if (const char *why = trials_unsupported(base, K, S, R))
+    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, std::string("vbhem_em_run_trials: ") + why);
+  for (int r = 1; r < R; ++r)
+    if (!post_ok(&posts[r]) || posts[r].K != K || posts[r].S != S || posts[r].d != d ||
+        posts[r].covmode != cov)
+      return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: the trials' posteriors differ in shape");
+  const size_t need = vbhem_em_trials_workspace_bytes(base, K, S, R, T);
+  if (need == 0)
+    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, "vbhem_em_run_trials: no batched E-step for this shape");
+  if (!workspace_dev || workspace_bytes < need) return VBHEM_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int N = base->N, RK = R * K;
+  const size_t dd = cov == VBHEM_COV_FULL ? (size_t)d * d : (size_t)d, KS = (size_t)K * S;
+  vbhem_cluster_t c0 = {RK, S, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const size_t fused = (vbhem_fused_trials_workspace_bytes(base, &c0, R, T) + 255) / 256 * 256;
+  const size_t slen = vbhem_stats_len(K, S, d, cov), postn = post_len(K, S, d, dd);
+  // per trial: logA | logPi | m | P | c | logOmega, stored trial-major array by array
+  const size_t nA = KS * S, nPi = KS, nm = KS * d, nP = KS * dd, nc = KS, nO = (size_t)K;
+  const size_t consts = (size_t)R * (nA + nPi + nm + nP + nc + nO);
+  double *p = reinterpret_cast<double *>(static_cast<char *>(workspace_dev) + fused);
+  double *dc = p; p += consts;
+  double *dbackup = p; p += consts;
+  double *dposts = p; p += 2 * (size_t)R * postn;
+  double *dlLT = p; p += (size_t)R * KS;
+  double *dlogdetW = p; p += (size_t)R * KS;
+  double *dpart = p; p += (size_t)R * KS * 13;
+  double *dstats = p; p += (size_t)R * slen;
+  double *dstats_out = p; p += (size_t)R * slen;
+  double *dhz = p; p += (size_t)N * RK;
+  double *dll = p; p += (size_t)N * RK;
+  double *dm0 = p; p += d;
+  double *dW0inv = p; p += (size_t)d * d;
+  vbhem::TrialCtrl *dctrl = reinterpret_cast<vbhem::TrialCtrl *>(p);
+  p += ((size_t)R * sizeof(vbhem::TrialCtrl) + 7) / 8;
+  int *dticket = reinterpret_cast<int *>(p);
+  vbhem_cluster_t cl = {RK, S, dc, dc + R * nA, dc + R * (nA + nPi), dc + R * (nA + nPi + nm),
+                        dc + R * (nA + nPi + nm + nP)};
+  double *dlogOmega = dc + R * (nA + nPi + nm + nP + nc);
+
+  std::vector<double> W0inv;
+  w0_inv(opt, d, W0inv);
+  const int ldL = opt->max_iter + 1;
+  vbhem::EmTrialsArgs t{};
+  vbhem::EmDevArgs &a = t.a;
+  a.K = K; a.S = S; a.d = d; a.covmode = cov; a.NU = (int)vbhem_stats_nu(d, cov);
+  a.stats = dstats;
+  a.alpha0 = opt->alpha0; a.eta0 = opt->eta0; a.epsilon0 = opt->epsilon0; a.lambda0 = opt->lambda0;
+  a.v0 = opt->v0;
+  bound_constants(opt, K, S, d, W0inv, a.logCalpha0, a.logCeta0, a.logCepsilon0, a.logB0);
+  a.m0 = dm0; a.W0inv = dW0inv;
+  a.logA = dc; a.logPi = dc + R * nA; a.cm = dc + R * (nA + nPi); a.P = dc + R * (nA + nPi + nm);
+  a.c = dc + R * (nA + nPi + nm + nP); a.lLT = dlLT;
+  a.logOmega = dlogOmega; a.logdetW = dlogdetW; a.part = dpart;
+  {
+    double *q = dposts;
+    const PostDev p0 = carve_post(q, K, S, d, dd);  // trial 0, buffer 0
+    a.alpha = p0.alpha; a.eta = p0.eta; a.eps = p0.eps; a.lam = p0.lam; a.v = p0.v; a.m = p0.m;
+    a.W = p0.W;
+  }
+  t.R = R; t.N = N; t.postn = postn; t.stats_len = slen; t.ctrl = dctrl; t.ticket = dticket;
+  t.ldL = ldL; t.max_iter = opt->max_iter; t.minDiff = opt->minDiff;
+  t.backup = dbackup; t.hz = dhz; t.ll = dll; t.hz_out = hatZ_dev; t.ll_out = LL_dev;
+  t.stats_out = dstats_out;
+
+  // the initial posteriors, packed as buffer 0 of every trial, and the records
+  std::vector<double> hp(2 * (size_t)R * postn);
+  const size_t fn[7] = {(size_t)K, KS, KS * S, KS, KS, KS * d, KS * dd};
+  for (int r = 0; r < R; ++r) {
+    const double *src[7] = {posts[r].alpha, posts[r].eta, posts[r].epsilon, posts[r].lam,
+                            posts[r].v, posts[r].m, posts[r].W};
+    double *q = hp.data() + (size_t)r * postn;
+    for (int x = 0; x < 7; ++x) {
+      std::copy(src[x], src[x] + fn[x], q);
+      q += fn[x];
+    }
+  }
+  std::vector<vbhem::TrialCtrl> ctrl((size_t)R);
+  for (int r = 0; r < R; ++r) vbhem::trial_ctrl_init(&ctrl[(size_t)r]);
+  // mapped host memory: flag[2] | active[2] | (64 bytes in) the bounds [R][max_iter + 1]
+  MappedBuf mb;
+  const size_t nL = (size_t)R * ldL;
+  hipError_t e = acquire_mapped_buf(64 + nL * sizeof(double), mb);
+  int *flag_h = reinterpret_cast<int *>(mb.h), *act_h = flag_h ? flag_h + 2 : nullptr;
+  double *L_h = mb.h ? reinterpret_cast<double *>(mb.h + 64) : nullptr;
+  if (e == hipSuccess) {
+    flag_h[0] = flag_h[1] = 0;
+    act_h[0] = act_h[1] = 0;
+    std::fill(L_h, L_h + nL, 0.0);
+    t.flag = reinterpret_cast<int *>(mb.d);
+    t.active = t.flag + 2;
+    t.LogLs = reinterpret_cast<double *>(mb.d + 64);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(dm0, opt->m0, d * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dW0inv, W0inv.data(), W0inv.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dposts, hp.data(), (size_t)R * postn * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dctrl, ctrl.data(), ctrl.size() * sizeof(vbhem::TrialCtrl), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(dticket, 0, (size_t)R * sizeof(int), st);
+  if (e == hipSuccess) e = vbhem::launch_em_trials(t, vbhem::kEmPrelude, st);
+  if (e == hipSuccess) e = vbhem::launch_trials_latch(t, -1, st);
+  int rc = VBHEM_OK;
+  // iteration j: the E-step of all R K clusters, every running trial's bound + M-step
+  // + prelude + decision, the latch and the word
+  auto enqueue = [&](int j) -> bool {
+    rc = vbhem_estep_fused_trials(base, &cl, R, T, tildeN_dev, dlogOmega, dstats, dhz, dll,
+                                  workspace_dev, fused, st);
+    if (rc != VBHEM_OK) return false;
+    e = vbhem::launch_em_trials(t, vbhem::kEmIterate, st);
+    if (e == hipSuccess) e = vbhem::launch_trials_latch(t, j, st);
+    return e == hipSuccess;
+  };
+  bool ok = e == hipSuccess && enqueue(0);
+  bool finished = false;
+  for (int j = 0; ok; ++j) {
+    // the next iteration is queued before this one's word is read; it changes nothing
+    // of a trial that this one stopped
+    if (j + 1 <= opt->max_iter && !enqueue(j + 1)) break;
+    e = wait_flag(flag_h + (j & 1), j + 1, st);
+    if (e != hipSuccess) break;
+    if (__atomic_load_n(act_h + (j & 1), __ATOMIC_ACQUIRE) == 0) {
+      finished = true;
+      break;
+    }
+    if (j == opt->max_iter) break;  // every trial stops at max_iter: not reached
+  }
+  hipError_t e2 = hipStreamSynchronize(st);  // the iteration queued ahead drains
+  if (e == hipSuccess) e = e2;
+  if (e == hipSuccess && rc == VBHEM_OK)
+    e = hipMemcpyAsync(hp.data(), dposts, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == VBHEM_OK)
+    e = hipMemcpyAsync(ctrl.data(), dctrl, ctrl.size() * sizeof(vbhem::TrialCtrl), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == VBHEM_OK)
+    e = hipMemcpyAsync(stats_out, dstats_out, (size_t)R * slen * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == VBHEM_OK) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rc == VBHEM_OK) std::copy(L_h, L_h + nL, LogLs);
+  if (e == hipSuccess) release_mapped_buf(mb);  // a failed stream may still write it: not reused
+  if (rc != VBHEM_OK) return rc;
+  if (e != hipSuccess) return vbhem::hip_fail(e, "vbhem_em_run_trials");
+  if (!finished)
+    return vbhem::set_error(VBHEM_ERR_HIP, "vbhem_em_run_trials: trials still running after max_iter + 1 iterations");
+  for (int r = 0; r < R; ++r) {
+    const vbhem::TrialCtrl &c = ctrl[(size_t)r];
+    iters[r] = c.it;
+    L_final[r] = c.L_final;
+    stable[r] = c.stable;
+    double *dst[7] = {posts[r].alpha, posts[r].eta, posts[r].epsilon, posts[r].lam,
+                      posts[r].v, posts[r].m, posts[r].W};
+    const double *q = hp.data() + ((size_t)c.cur * R + r) * postn;
+    for (int x = 0; x < 7; ++x) {
+      std::copy(q, q + fn[x], dst[x]);
+      q += fn[x];
+    }
+  }
+  return VBHEM_OK;
 }
 
 }  // extern "C"

@@ -36,4 +36,44 @@ bool em_dev_supported(int d, int S);
 // host), then the M-step of (stats) into (alpha_o .. W_o) and its prelude.
 hipError_t launch_em_dev(const EmDevArgs &a, int mode, double *L_out, hipStream_t st);
 
+// ---- R trials in one launch, stopped on the device (vbhem_em_trials.hip) ----
+struct TrialCtrl;  // vbhem_em_trial_ctrl.h
+
+// `a` holds the shapes (K = clusters of ONE trial), the hyperparameters and the
+// pointers of trial 0: its posterior buffer 0 in (alpha .. W) -- buffer b of trial r
+// lies (b R + r) postn doubles further, the M-step outputs are not used -- and its
+// slices of the trial-major arrays, trial r lying r times the slice further: the
+// cluster constants logA [R K][S][S], logPi, cm, P, c (what the batched E-step
+// reads), logOmega [R K], lLT, logdetW [R K S], part [R][13][K S] and the statistics
+// [R][stats_len].  a.ticket, a.flag and a.seq are not used.
+struct EmTrialsArgs {
+  EmDevArgs a;
+  int R, N;           // trials; base HMMs (rows of hat_Z)
+  size_t postn;       // doubles of one posterior
+  size_t stats_len;   // doubles of one trial's packed statistics
+  TrialCtrl *ctrl;    // [R]
+  int *ticket;        // [R], 0 between launches
+  double *LogLs;      // [R][ldL]: the accepted bounds (device, or mapped host memory)
+  int ldL, max_iter;  // ldL >= max_iter + 1
+  double minDiff;
+  // the latch: a copy of every running trial's E-step constants (logA | logPi | cm |
+  // P | c | logOmega, laid out as the live ones), the E-step's outputs and where a
+  // stopping trial's columns and statistics are kept
+  double *backup;
+  const double *hz, *ll;            // [N][R K], overwritten by every E-step
+  double *hz_out, *ll_out;          // [N][R K]
+  double *stats_out;                // [R][stats_len]
+  int *flag, *active;               // [2] each (mapped host memory), slot j % 2
+};
+
+// kEmPrelude: the prelude of every trial's buffer 0.  kEmIterate: for every trial
+// not done, the bound of its current posterior, the M-step into its other buffer,
+// that one's prelude, and trial_ctrl_step on the bound.
+hipError_t launch_em_trials(const EmTrialsArgs &t, int mode, hipStream_t st);
+// After iteration j (j = -1 after the prelude: no word): keeps the E-step outputs
+// and statistics of every trial that stopped at j, saves the constants of every
+// running trial and puts back those of a trial whose bound was NaN, then writes
+// active[j % 2] = trials not done and flag[j % 2] = j + 1.
+hipError_t launch_trials_latch(const EmTrialsArgs &t, int j, hipStream_t st);
+
 }  // namespace vbhem

@@ -142,13 +142,27 @@ class TrialsResult:
 def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *,
                        total_N: Optional[int] = None,
                        allreduce: Optional[Callable[[torch.Tensor], None]] = None,
-                       max_iter: Optional[int] = None) -> TrialsResult:
+                       max_iter: Optional[int] = None, em_engine: str = "host") -> TrialsResult:
     """R EM trials from their own initial posteriors (vbhem_h3m_c.m:28-67,
     `parfor it = 1:numits`), run in lockstep with one batched E-step launch per
     iteration (vbhem_estep_fused_trials).  Every trial follows
     :func:`vbhem_h3m_c_step_fc` exactly; a trial that has stopped keeps its
     final state (its clusters still ride along in the launch, their outputs
-    unused).  The best trial is the one with the largest final bound."""
+    unused).  The best trial is the one with the largest final bound.
+
+    em_engine: ``"host"`` (the default) runs the bound, the M-step, the prelude
+    and the stopping rule of every trial in numpy between two launches;
+    ``"device"`` runs them on the GPU as well (:func:`vbhem_amd.native_em.run_trials`:
+    one rank, a device :class:`EStepEngine`, R K <= 256, Sb <= S <= 16, d <= 16)."""
+    if em_engine not in ("host", "device"):
+        raise ValueError(f"em_engine {em_engine!r}: 'host' or 'device'")
+    if em_engine == "device":
+        if allreduce is not None:
+            raise ValueError("em_engine='device' runs on one rank: no allreduce")
+        if not isinstance(engine, EStepEngine):
+            raise ValueError("em_engine='device' needs a device EStepEngine")
+        from . import native_em
+        return native_em.run_trials(posts, engine, opt, max_iter, total_N=total_N)
     R = len(posts)
     if engine.trials != R:
         raise ValueError("engine.trials must equal len(posts)")

@@ -194,6 +194,70 @@ def run(post: Posterior, engine: EStepEngine, opt: dict, *, total_N: Optional[in
     return res
 
 
+def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = None, *,
+               total_N: Optional[int] = None):
+    """R EM trials of one (K, S) cell in one device-side loop (vbhem_em_run_trials):
+    per iteration the batched E-step, one kernel with every trial's bound, M-step,
+    prelude and stopping rule, and one that keeps what the stopping trials leave;
+    the host only waits for a word per iteration.  ``engine`` is a device
+    :class:`EStepEngine` with ``trials == len(posts)``.  Returns what
+    :func:`vbhem_amd.em.vbhem_h3m_c_trials` returns (an unstable trial's ``syn`` is
+    None).  One rank; no bound derivatives."""
+    from . import host
+    from .em import TrialsResult, tilde_n
+    if not isinstance(engine, EStepEngine):
+        raise ValueError("native_em.run_trials needs a device EStepEngine")
+    R = len(posts)
+    if R < 1 or engine.trials != R:
+        raise ValueError("engine.trials must equal len(posts)")
+    covmode = engine.base.covmode
+    total_N = engine.N if total_N is None else int(total_N)
+    opt = dict(opt)
+    if max_iter is not None:
+        opt["max_iter"] = int(max_iter)
+    pbs = [_PostBuf(P, covmode) for P in posts]
+    ob = _OptBuf(opt)
+    K, S = pbs[0].t.K, pbs[0].t.S
+    d = pbs[0].a["m"].shape[2]
+    if any((pb.t.K, pb.t.S, pb.a["m"].shape[2]) != (K, S, d) for pb in pbs) or engine.K != R * K:
+        raise ValueError("the trials' posteriors must share one shape, K = engine.K / trials")
+    post_arr = (_capi.PostT * R)(*[pb.t for pb in pbs])
+    tN = tilde_n(engine, opt["Nv"], total_N).contiguous()
+    lib = _capi.lib()
+    nb = int(lib.vbhem_em_trials_workspace_bytes(ctypes.byref(engine._bt), K, S, R, engine.T))
+    if nb == 0:
+        raise _capi.VbhemError(
+            f"vbhem_em_trials_workspace_bytes: unsupported shape (R={R}, K={K}, S={S}, d={d}, "
+            f"Sb={engine.base.SB}): needs R*K <= 256, Sb <= S <= 16, d <= 16")
+    ws = _workspace(engine, nb)
+    ld = int(opt["max_iter"]) + 1
+    SL = int(lib.vbhem_stats_len(K, S, d, covmode))
+    LogLs = np.zeros((R, ld))
+    iters, stable = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+    Lf = np.zeros(R)
+    stats = np.zeros((R, SL))
+    rc = lib.vbhem_em_run_trials(ctypes.byref(engine._bt), _capi.ptr(tN), R, engine.T,
+                                 ctypes.byref(ob.t), post_arr, _p(LogLs), _p(iters), _p(Lf),
+                                 _p(stable), _p(stats), _capi.ptr(engine.hatZ), _capi.ptr(engine.LL),
+                                 _capi.ptr(ws), ws.numel(), engine._stream())
+    _capi.check(rc, "vbhem_em_run_trials")
+    results = []
+    for r in range(R):
+        it, ok = int(iters[r]), bool(stable[r])
+        cols = slice(r * K, (r + 1) * K)
+        st = host.unpack_stats(stats[r], K, S, d, covmode)
+        res = EMResult(post=pbs[r].posterior(), LogLs=[float(x) for x in LogLs[r, :it]],
+                       LL=float(Lf[r]), iters=it, stable=ok, hatZ=engine.hatZ[:, cols].clone(),
+                       L_elbo=engine.LL[:, cols].clone(), Nj=st["Nj"] + 1e-50,
+                       syn=host.finish_statistics(st, covmode) if ok else None)
+        if ok:
+            res.point = host.convert_to_point(res.post, covmode)
+            res.label = torch.argmax(res.hatZ, dim=1)
+        results.append(res)
+    LLall = np.array([x.LL for x in results])
+    return TrialsResult(results=results, LLall=LLall, best=int(np.argmax(LLall)))
+
+
 def _raw_dict(g: np.ndarray, nW: int) -> dict:
     return {"alpha0": g[0:1].copy(), "eta0": g[1:2].copy(), "epsilon0": g[2:3].copy(),
             "v0": g[3:4].copy(), "lambda0": g[4:5].copy(), "W0": g[5:5 + nW].copy(),

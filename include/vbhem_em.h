@@ -121,6 +121,33 @@ int vbhem_em_run_ext(const vbhem_base_t *base, const double *tildeN_dev, int T,
                      double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
                      vbhem_allreduce_fn allreduce, void *allreduce_ctx, const vbhem_em_ext_t *ext);
 
+/* The R EM trials of one (K, S) cell (vbhem_h3m_c.m:28-67, `parfor it = 1:numits`) in
+ * one loop that never leaves the device: per iteration one vbhem_estep_fused_trials
+ * launch over the R * KT clusters, one kernel with the bound, the M-step, the next
+ * prelude and the stopping rule of every trial (vbhem_em_trials.hip; the rule is
+ * vbhem_em_run's, per trial), and one that keeps the outputs of the trials that
+ * stopped.  A trial that has stopped is frozen on the device (its clusters ride along
+ * in the later E-steps, their outputs unused), so the one iteration the host queues
+ * ahead of the word it waits for cannot change a result; never more than
+ * max_iter + 1 iterations are queued.  One rank only: no all-reduce, no derivatives.
+ *
+ * Shapes: those of vbhem_estep_fused_trials (S <= 16, Sb <= S, R * KT <= 256) with
+ * d <= 16; vbhem_em_trials_workspace_bytes returns 0 for any other, and
+ * vbhem_em_run_trials VBHEM_ERR_UNSUPPORTED (vbhem_last_error says which limit).
+ *
+ * posts: R host posteriors of KT clusters each (in: the initialisations; out: the
+ * posteriors after each trial's last accepted M-step; a trial whose first bound is
+ * NaN keeps its input).  LogLs [R][max_iter + 1], iters / L_final / stable [R]: per
+ * trial as vbhem_em_run's.  stats_out [R][vbhem_stats_len(KT, ...)] (host): the packed
+ * statistics of each trial's stopping iteration.  hatZ_dev / LL_dev [N][R * KT]
+ * (device): trial r's columns [r KT, (r + 1) KT) hold hat_Z and L_elbo of the E-step of
+ * ITS stopping iteration. */
+size_t vbhem_em_trials_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T);
+int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
+                        const vbhem_em_opt_t *opt, vbhem_post_t *posts, double *LogLs, int *iters,
+                        double *L_final, int *stable, double *stats_out, double *hatZ_dev,
+                        double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* vbhemh3m_lb.m:202-345: the raw derivatives of the bound with respect to the
  * hyperparameters (posterior held fixed; no clipping, no change of variables --
  * vbhem_amd/hyp.py applies :326-356), from the posterior and its prelude outputs. */
