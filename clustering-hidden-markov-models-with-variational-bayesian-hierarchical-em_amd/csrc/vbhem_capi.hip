@@ -20,6 +20,7 @@
 #include "vbhem_estep_plan.h"
 #include "vbhem_estep_sched.h"
 #include "vbhem_internal.h"
+#include "vbhem_stats_plan.h"
 
 namespace {
 

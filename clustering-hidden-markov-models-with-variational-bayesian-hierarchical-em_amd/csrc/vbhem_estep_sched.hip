@@ -12,6 +12,7 @@
 #include "vbhem_estep_plan.h"
 #include "vbhem_estep_sched.h"
 #include "vbhem_internal.h"
+#include "vbhem_stats_plan.h"
 
 namespace {
 
@@ -293,6 +294,7 @@ int run_fb_exact(const FbArgs &a, double *scratch, hipStream_t st) {
 int run_fb_list(const FbCtx &c, const Pass &p, const double *Ebuf, long long e_ld, const int *list,
                 const int *list_tot, int list_cap, double *scratch, hipStream_t st,
                 bool fold = false, bool *inlined = nullptr, const StatsArgs *acc_sa = nullptr,
+                const GatedPlan *acc_plan = nullptr, const StatsShape *acc_shape = nullptr,
                 double *acc_parts = nullptr, int *acc_waves = nullptr) {
   if (p.i_end <= p.i_begin) return VBHEM_OK;
   // flags[0] is zero here: the backward pass's fb_exact_kernel reset it
@@ -309,14 +311,13 @@ int run_fb_list(const FbCtx &c, const Pass &p, const double *Ebuf, long long e_l
   // persistent grid has a scratch slot per wavefront (then no launch after the pass)
   ca.xinline = 0;
   // fb_list4_kernel's statistics-accumulating variant (acc_sa: this group's statistics
-  // arguments): the weights, the statistics copy of a prepared operand and a shape within
-  // its tiles; it needs the inline fallback, which it may take without the fold as well
-  // (several base groups) unless the fold was switched off
+  // arguments; acc_plan, acc_shape: the call's gated-statistics plan): only where
+  // stats_list_m_kernel would otherwise sum them (list4_acc_eligible); it needs the
+  // inline fallback, which it may take without the fold as well (several base groups)
+  // unless the fold was switched off
   const Switches &sw = switches();
-  const bool acc = c.list_kernel == ListKernel::kList4 && acc_sa && acc_parts && acc_sa->Us &&
-                   acc_sa->Z && !acc_sa->vhem &&
-                   list4_acc_supported(ca.S, ca.SB, ca.T, ca.K, acc_sa->NU) &&
-                   !sw.NO_LIST4_STATS && !sw.NO_STATS_M && !sw.NO_STATS_U;
+  const bool acc = c.list_kernel == ListKernel::kList4 && acc_sa && acc_plan && acc_shape && acc_parts &&
+                   list4_acc_eligible(*acc_plan, *acc_shape, ca.T, acc_sa->Z != nullptr, sw);
   if (acc_waves) *acc_waves = 0;
   auto set_inline = [&](long long waves) {
     if (!(fold || (acc && !sw.NO_FOLD_EXACT)) || waves > kExactThreads || sw.NO_LIST_INLINE) return;
@@ -556,24 +557,30 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
     sa.omegaB = vh->omegaB;
     sa.inf_norm = vh->inf_norm;
   }
-  size_t slds = 0;
-  int ngroups = 1;
-  const bool dense_ok = plan_stats(sa, slds, ngroups);  // dense-schedule statistics
 
   FbCtx ctx;
   int rc = prepare_fb(ctx, base, clus, T, vh ? vh->smooth : 1.0, vh != nullptr);
   if (rc != VBHEM_OK) return rc;
   ctx.u_ws = w.U;
-  // gated schedule: split kernel + list statistics tile must apply
-  size_t sl_lds = 0;
-  // (gate lists: per-wave ballot masks of all K clusters in LDS, K up to ~2,400)
   const Switches &sw = switches();  // this thread's set, fixed for the call
-  const bool gated = !sw.FUSED_DENSE && ctx.split.ok && ctx.split.lds_l &&
-                     plan_stats_list(sa, sl_lds) && gate_list_lds(K) <= kLdsLimit;
+  // the epilogue's plans (vbhem_stats_plan.h), once per call.  The emission GEMM's operand
+  // serves the statistics too: the prepared one with its statistics copy, or the one
+  // run_fb builds per group
+  const bool opnd = ctx.split.ok && ctx.use_u;
+  const StatsShape shape{K, K / R, S, SB, d, base->covmode, opnd ? ctx.em.kdp : 0,
+                         opnd && (base->U || ctx.u_ws), opnd && base->U, vh != nullptr};
+  const DensePlan dense = plan_stats_dense(shape);
+  sa.SBp = dense.SBp; sa.UST = dense.UST; sa.JG = dense.JG; sa.NBB = dense.NBB; sa.AST = dense.AST;
+  const GatedPlan gplan = plan_stats_gated(shape, std::min(base->N, w.group), sw);
+  sa.PB = gplan.PB;
+  // gated schedule: split kernel + list statistics tile must apply
+  // (gate lists: per-wave ballot masks of all K clusters in LDS, K up to ~2,400)
+  const bool gated = !sw.FUSED_DENSE && ctx.split.ok && ctx.split.lds_l && gplan.ok &&
+                     gate_list_lds(K) <= kLdsLimit;
   if (R > 1 && !gated)
     return set_error(VBHEM_ERR_UNSUPPORTED,
                      "trials need the gated schedule (split-kernel shapes: S <= 16, Sb <= S)");
-  if (!gated && !dense_ok)
+  if (!gated && !dense.ok)
     return set_error(VBHEM_ERR_UNSUPPORTED, "statistics tile does not fit (S or d too large)");
   sa.gate_cnt = gated ? w.gate_cnt : nullptr;
   sa.list = w.list; sa.list_tot = w.list_tot; sa.list_cap = w.group;
@@ -624,6 +631,8 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
   const bool fold = gated && R == 1 && base->N <= w.group && ctx.split.ok && K < kExactThreads &&
                     w.nslab <= kExactThreads && !sw.NO_FOLD_EXACT;
   sa.fold = 0;
+  const RespPlan resp = plan_resp(shape, fold, sw);
+  const GatedPlan l4reduce = plan_list4_reduce(shape);
   for (int g0 = 0; g0 < base->N; g0 += w.group) {
     const int g1 = std::min(base->N, g0 + w.group);
     const long long e_ld = (long long)w.group * SB;
@@ -649,7 +658,7 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
     }
     const int nchunk = std::max(1, chunks(g1 - g0));
     hipEvent_t ev0 = timing_start(st);
-    e = launch_resp(sa, nchunk, st);
+    e = launch_resp(sa, resp, nchunk, st);
     if (e != hipSuccess) return hip_fail(e, "resp_kernel");
     if (gated) {
       e = launch_gate_list(sa, nchunk, st);
@@ -658,24 +667,26 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
       bool inl = false;
       int l4w = 0;  // > 0: fb_list4_kernel accumulated the statistics, on that many waves
       rc = run_fb_list(ctx, pass, w.E, e_ld, w.list, w.list_tot, w.group, w.scratch, st, fold, &inl,
-                       &sa, w.l4parts, &l4w);
+                       &sa, &gplan, &shape, w.l4parts, &l4w);
       if (rc != VBHEM_OK) return rc;
       if (fold) sa.fold = inl ? 2 : 1;  // 2: no fb_exact_kernel launch before the statistics
       ev0 = timing_start(st);
-      int ss = nchunk;
+      int ss = 0;
       if (l4w > 0) {
-        ss = 1;
+        ss = l4reduce.stats_slabs;
         g_last_kernel[2] = "vbhem::list4_stats_reduce_kernel";
-        e = launch_list4_stats_reduce(sa, w.l4parts, l4w, st);
+        e = launch_list4_stats_reduce(sa, l4reduce, w.l4parts, l4w, st);
         if (e != hipSuccess) return hip_fail(e, "list4_stats_reduce_kernel");
       } else {
+        const GatedPlan gp = plan_gated_group(gplan, shape, nchunk, sa.nzero_m, sa.fold, sw);
+        ss = gp.stats_slabs;
         g_last_kernel[2] = "vbhem::stats_list_kernels";
-        e = launch_stats_list(sa, nchunk, sl_lds, st, &ss);
+        e = launch_stats_list(sa, gp, st);
       }
       if (e != hipSuccess) return hip_fail(e, "stats_list_kernel");
       if (g0 == 0) stats_slabs = ss;  // later groups add into [0, ss) with ss <= this
     } else {
-      e = launch_stats(sa, nchunk, ngroups, slds, st);
+      e = launch_stats(sa, dense, nchunk, st);
       if (e != hipSuccess) return hip_fail(e, "stats_kernel");
     }
     timing_stop(kTimeStats, ev0, st);

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 
 #include "vbhem_estep.h"     // status codes
 #include "vbhem_switches.h"  // struct Switches, switches()
@@ -413,9 +414,12 @@ hipError_t launch_list4(const SplitArgs &a, unsigned grid, hipStream_t st);
 // the statistics-accumulating variant (SplitArgs::acc) takes the shape: NU within
 // kL4sMaxTiles feature tiles
 bool list4_acc_supported(int S, int SB, int T, int K, int NU);
-// its reduction (vbhem_stats.hip): per cluster the partials of its slots summed in slot
-// order, shifted back by z and written (a.assign) or added to slab 0's N1 | M | U sections
-hipError_t launch_list4_stats_reduce(const StatsArgs &a, const double *parts, int nw, hipStream_t st);
+// its reduction (vbhem_stats_mfma.hip; gp: plan_list4_reduce's): per cluster the partials
+// of its slots summed in slot order, shifted back by z and written (a.assign) or added to
+// slab 0's N1 | M | U sections
+struct GatedPlan;
+hipError_t launch_list4_stats_reduce(const StatsArgs &a, const GatedPlan &gp, const double *parts, int nw,
+                                     hipStream_t st);
 
 // fb_list12_kernel (vbhem_fb_list12.hip): the gate-list pass for S = 12, SB <= 12, T = 10
 // (3 x 3 blocks of v_mfma_f64_4x4x4f64, the lattice in registers); fields as fb_list4_kernel
@@ -466,17 +470,26 @@ constexpr int kExactSlots = kExactBlocks * kExactBlock / 64;  // scratch slots: 
 hipError_t launch_fb_exact(const FbArgs &a, double *scratch, size_t stride, int nslots,
                            hipStream_t st, bool from_fold = false);
 hipError_t launch_emit(const EmitArgs &a, hipStream_t st);
-bool plan_stats(StatsArgs &a, size_t &lds, int &ngroups);
-hipError_t launch_resp(const StatsArgs &a, int nchunk, hipStream_t st);
-hipError_t launch_stats(const StatsArgs &a, int nchunk, int ngroups, size_t lds, hipStream_t st);
-bool plan_stats_list(StatsArgs &a, size_t &lds);
+// The epilogue's launchers, each on the plan that vbhem_stats_plan.h made for it
+// (vbhem_resp.hip, vbhem_stats_dense.hip, vbhem_stats_gated.hip, vbhem_stats_mfma.hip)
+struct RespPlan;
+struct DensePlan;
+// A launcher's switch over a plan's template bucket: f(std::integral_constant<int, V>)
+// for the V among Vs that equals v -- the kernel instance -- or null when none does
+using StatsKernel = void (*)(const StatsArgs);
+template <int... Vs, class F>
+StatsKernel pick_kernel(int v, F f) {
+  StatsKernel k = nullptr;
+  (void)((v == Vs && (k = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return k;
+}
+hipError_t launch_resp(const StatsArgs &a, const RespPlan &rp, int nchunk, hipStream_t st);
+hipError_t launch_stats(const StatsArgs &a, const DensePlan &dp, int nchunk, hipStream_t st);
 hipError_t launch_gate_list(const StatsArgs &a, int nchunk, hipStream_t st);
-size_t gate_list_lds(int K);  // dynamic LDS of gate_list_kernel for K clusters
-size_t resp_lds(int K, int KT);  // dynamic LDS of resp_kernel / resp_trials_kernel
-size_t vhem_resp_lds(int K, int KT);  // dynamic LDS of vhem_resp_kernel
-// *stats_slabs (optional): the slabs [0, n) holding this launch's N1 / M / U entries
-hipError_t launch_stats_list(const StatsArgs &a, int nchunk, size_t lds, hipStream_t st,
-                             int *stats_slabs = nullptr);
+// the gated sums of one base group (gp: plan_gated_group's), after an fb_exact_kernel
+// launch for the gate-list pass's flagged pairs when the plan asks for one
+hipError_t launch_stats_list(const StatsArgs &a, const GatedPlan &gp, hipStream_t st);
+StatsKernel stats_mfma_kernel(const GatedPlan &gp);  // stats_list_m_kernel's instance (vbhem_stats_mfma.hip)
 // sums slabs [0, nslab) of the Nj / Lt1 / Lt7 columns (resp_kernel's per-chunk partials)
 // and slabs [0, nslab_stats) of the N1 / M / U columns (KT clusters x S states per
 // section of SL doubles)

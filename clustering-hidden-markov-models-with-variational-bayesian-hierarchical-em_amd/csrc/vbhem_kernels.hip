@@ -15,7 +15,7 @@
 //                       step) for pairs whose factorised normaliser left its
 //                       safe range (only with pathological hyperparameters).
 //   pair_emit_kernel    K5 per pair (MEX-equivalent emit_pr/mu/Mu outputs).
-//   (the fused epilogue -- responsibilities and statistics -- is in vbhem_stats.hip)
+//   (the fused epilogue -- responsibilities and statistics -- is in vbhem_resp.hip and vbhem_stats_*.hip)
 //
 // Factorised backward step (exact algebra):
 //   l(rho,sig,b) = logA(rho,sig) + v(sig,b),  v = E + L

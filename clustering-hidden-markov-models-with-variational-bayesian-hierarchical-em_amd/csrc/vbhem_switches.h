@@ -32,7 +32,6 @@
   X(NO_STATS_G, 0, "gated statistics: no lane-grouped kernel")                                 \
   X(NO_STATS_U, 0, "gated statistics: the covariance-gather kernel")                           \
   X(NO_STATS_M, 0, "gated statistics: without stats_list_m_kernel")                            \
-  X(STATS_U, 0, "gated statistics: the prepared-operand kernel at any NU")                     \
   X(EM_HOST_MATH, 0, "the EM loop's per-iteration math on the host")
 
 namespace vbhem {

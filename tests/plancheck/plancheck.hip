@@ -1,10 +1,13 @@
-// tests/plancheck/plancheck.hip -- TEST-ONLY exports of the E-step's launch planner
-// (csrc/vbhem_estep_plan.h): every field of plan_split and plan_fb as integers and the
-// persistent-grid rule, so the geometry is checked on a machine without a GPU
-// (tests/test_estep_plan.py compares them with a recorded table).
+// tests/plancheck/plancheck.hip -- TEST-ONLY exports of the E-step's launch planners
+// (csrc/vbhem_estep_plan.h, csrc/vbhem_stats_plan.h): every field of plan_split and
+// plan_fb, of the epilogue's responsibility / dense / gated plans, and the block-count
+// rules as integers, so the geometry and the choice of kernel are checked on a machine
+// without a GPU (tests/test_estep_plan.py and tests/test_stats_plan.py compare them with
+// recorded tables).
 #include <hip/hip_runtime.h>
 
 #include "vbhem_estep_plan.h"
+#include "vbhem_stats_plan.h"
 
 namespace {
 
@@ -62,6 +65,61 @@ void plancheck_fb(int SB, int d, int covmode, int K, int S, int T, long long *ou
 
 long long plancheck_persistent_blocks(long long tiles, long long resident, long long K) {
   return persistent_blocks((unsigned)tiles, (unsigned)resident, (unsigned)K);
+}
+
+// ---- the epilogue's planner (csrc/vbhem_stats_plan.h) ----
+// out [11]: ok ngroups lds SBp UST JG NBB AST TPW nm_per nm_unr
+void plancheck_stats_dense(int K, int S, int SB, int d, int covmode, long long *out) {
+  const DensePlan p = plan_stats_dense(StatsShape{K, K, S, SB, d, covmode, 0, false, false, false});
+  const long long v[11] = {p.ok, p.ngroups, (long long)p.lds, p.SBp, p.UST, p.JG, p.NBB, p.AST,
+                           p.TPW, p.nm_per, p.nm_unr};
+  for (int k = 0; k < 11; ++k) out[k] = v[k];
+}
+
+// out [5]: ok kernel (RespKernel) KP lds, then gate_list_lds(K)
+void plancheck_resp(int K, int KT, int S, int SB, int vhem, int fold, int generic, long long *out) {
+  Switches sw;
+  sw.RESP_GENERIC = generic;
+  const RespPlan p = plan_resp(StatsShape{K, KT, S, SB, 2, kCovFull, 0, false, false, vhem != 0},
+                               fold != 0, sw);
+  const long long v[5] = {p.ok, (long long)p.kernel, p.KP, (long long)p.lds, (long long)gate_list_lds(K)};
+  for (int k = 0; k < 5; ++k) out[k] = v[k];
+}
+
+namespace {
+// out [16]: ok kernel (GatedStats) NTW G KSM NXR LG SM PER PB lds cap nzero stats_slabs
+// exact_first, then the blocks along x that the launcher asks for
+void gated_out(const GatedPlan &p, int K, long long resident, const Switches &sw, long long *out) {
+  const long long blocks = p.kernel == GatedStats::kMfma ? stats_m_blocks(resident, K, p.cap, sw)
+                         : p.kernel == GatedStats::kList4Reduce ? (long long)K * p.cap : p.cap;
+  const long long v[16] = {p.ok, (long long)p.kernel, p.NTW, p.G, p.KSM, p.NXR, p.LG, p.SM, p.PER, p.PB,
+                           (long long)p.lds, p.cap, p.nzero, p.stats_slabs, p.exact_first, blocks};
+  for (int k = 0; k < 16; ++k) out[k] = p.ok ? v[k] : 0;  // (zeros: refused)
+}
+}  // namespace
+
+// opnd: 0 no operand, 1 U only, 2 U and its statistics copy Us; sw [4]: NO_STATS_M
+// NO_STATS_U NO_STATS_G SU_BLOCKS
+void plancheck_stats_gated(int K, int S, int SB, int d, int covmode, int opnd, int nchunk,
+                           long long nbases, long long resident, int fold, int nzero_m,
+                           const long long *swv, long long *out) {
+  Switches sw;
+  sw.NO_STATS_M = swv[0]; sw.NO_STATS_U = swv[1]; sw.NO_STATS_G = swv[2]; sw.SU_BLOCKS = swv[3];
+  const StatsShape s{K, K, S, SB, d, covmode, opnd ? emission_kdp(d, covmode) : 0, opnd >= 1, opnd >= 2, false};
+  GatedPlan p = plan_stats_gated(s, nbases, sw);
+  if (p.ok) p = plan_gated_group(p, s, nchunk, nzero_m, fold, sw);
+  gated_out(p, K, resident, sw, out);
+}
+
+void plancheck_list4_reduce(int K, int S, int d, int covmode, long long *out) {
+  const StatsShape s{K, K, S, S, d, covmode, emission_kdp(d, covmode), true, true, false};
+  gated_out(plan_list4_reduce(s), K, 0, Switches{}, out);
+}
+
+long long plancheck_stats_m_blocks(long long resident, int K, int cap, long long su_blocks) {
+  Switches sw;
+  sw.SU_BLOCKS = su_blocks;
+  return stats_m_blocks(resident, K, cap, sw);
 }
 
 }  // extern "C"

@@ -137,18 +137,15 @@ def test_stats_on_prepared_operand(vb, name, prepare):
     N = max(N, 40)
     cs = make_case(N, K, S, Sb, d, cov, seed=11 + len(name), **extra)
     outs = []
-    # VBHEM_STATS_U=1: the prepared-operand kernel also where the default picks the
-    # covariance path (NU > 64)
     # VBHEM_NO_STATS_G=1: the one-pair-per-wave kernel where the grouped one (small NU)
     # is the default
     # default (prepared): the MFMA kernel on the statistics copy Us, also with one block
     # per cluster (> 64 pairs per wave: the list-base refetch); VBHEM_NO_STATS_M=1: the
-    # older prepared-operand kernels
+    # older prepared-operand kernels (up to NU = 64; past it the covariance gather)
+    # (which kernel each set reaches: tests/test_stats_plan.py)
     no_m = {"VBHEM_NO_STATS_M": "1"}
-    for env in ({"VBHEM_NO_STATS_U": "1"}, {"VBHEM_STATS_U": "1", **no_m},
-                {"VBHEM_STATS_U": "1", "VBHEM_SU_BLOCKS": str(K), **no_m},
-                {"VBHEM_STATS_U": "1", "VBHEM_NO_STATS_G": "1", **no_m},
-                {}, {"VBHEM_SU_BLOCKS": str(K + 1)}):
+    for env in ({"VBHEM_NO_STATS_U": "1"}, no_m, {"VBHEM_SU_BLOCKS": str(K), **no_m},
+                {"VBHEM_NO_STATS_G": "1", **no_m}, {}, {"VBHEM_SU_BLOCKS": str(K + 1)}):
         with _capi.switches(GROUP_BASES=N // 2 + 1, **env):
             eng = EStepEngine(cs["bs"], K, S, cs["T"], device=DEV, prepare=prepare)
             eng.set_clusters(cs["consts"])
