@@ -122,6 +122,59 @@ STATE_COUNT_SHAPES = [
 ]
 
 
+# the cluster counts K that the single-call shapes above leave out (they stop at K in {1..6, 8,
+# 16, 32}; same tuple layout; tests/test_cluster_count_cases.py, test_fused_cluster_counts_gpu.py).
+# The fused epilogue picks its path by K: resp_kernel<K> for K = 4, 8, 16, 32, 64 (a lane per
+# cluster, 64 / K bases per wave step, two steps pipelined), else resp_kernel<0> with G = the
+# power of two >= K lanes per base -- K <= G with the lanes past K masked, or K > 64 with a lane
+# holding the clusters gl, gl + 64, ...  A chunk is at least 64 bases: N = 131 gives chunks of
+# 44 / 44 / 43, N = 65 and 70 two.  Downstream of K: gate_list_kernel's ballot masks of all K
+# clusters (a second round of its j0 loop past K = 256), the (cluster, part) grid of
+# stats_list_m_kernel, stats_kernel's row groups (ngroups > 1 from K S > 128), stats_final_kernel
+# and nm_kernel
+CLUSTER_COUNT_SHAPES = [
+    ("K2_chunks", 131, 2, 3, 3, 2, 1, 5, True),      # G = 2: 32 bases per wave step, 3 chunks
+    ("K4_chunks", 131, 4, 3, 3, 2, 0, 5, False),     # resp_kernel<4>: chunks shorter than one step pair
+    ("K7", 131, 7, 3, 3, 2, 1, 5, True),             # G = 8, one masked lane
+    ("K9", 131, 9, 2, 3, 2, 0, 4, False),            # G = 16, 7 masked lanes
+    ("K15", 70, 15, 3, 3, 2, 1, 5, True),
+    ("K17", 131, 17, 3, 3, 2, 0, 5, True),           # G = 32
+    ("K31", 65, 31, 2, 2, 2, 1, 4, False),           # N = 65: a second chunk
+    ("K32_chunks", 131, 32, 3, 3, 2, 1, 5, True),    # resp_kernel<32>
+    ("K33", 131, 33, 3, 3, 2, 0, 5, True),           # G = 64, one base per step
+    ("K63", 65, 63, 2, 2, 2, 1, 4, False),
+    ("K64", 131, 64, 3, 3, 2, 1, 5, True),           # resp_kernel<64>
+    ("K64_one", 9, 64, 2, 2, 3, 0, 4, False),        # one short chunk: the second pipelined step all past its end
+    ("K65", 131, 65, 3, 3, 2, 1, 5, True),           # the K > 64 loop: lane 0 holds two clusters
+    ("K100", 70, 100, 2, 2, 2, 0, 4, False),
+    ("K129", 65, 129, 2, 2, 2, 1, 4, True),          # lanes hold 3 or 2 clusters
+    ("K257", 70, 257, 2, 2, 2, 0, 4, False),         # gate_list_kernel's second j0 round (KC = 1)
+    ("K13_S8", 45, 13, 8, 8, 3, 1, 10, True),        # fb_bwd4 / fb_list4 and the MFMA statistics at odd K
+    ("K33_S8", 45, 33, 8, 6, 2, 0, 10, True),
+    ("K17_S12", 37, 17, 12, 9, 3, 1, 10, True),      # fb_bwd12 / fb_list12
+    ("K65_S5", 70, 65, 5, 5, 2, 0, 10, False),       # the C3-like short-K1 path at K > 64
+]
+
+# batched trials, R trials of K_trial clusters as one set of R K_trial <= 256 clusters
+# (resp_trials_kernel: G lanes per base from the total, a lane holds the clusters gl + s G of
+# slots s < 4, a trial's clusters are consecutive and so cross lane 63 and the slots):
+# (name, N, K_trial, S, Sb, d, covmode, T, ragged, R)
+TRIAL_COUNT_SHAPES = [
+    ("t3x5", 131, 5, 3, 3, 2, 1, 5, True, 3),        # 15 clusters: G = 16, 4 bases per step
+    ("t9x3", 131, 3, 3, 3, 2, 0, 5, True, 9),        # 27: G = 32
+    ("t5x13", 70, 13, 3, 3, 2, 1, 5, True, 5),       # 65: one cluster in slot 1
+    ("t22x3", 131, 3, 3, 3, 2, 1, 5, True, 22),      # 66: trial 21 = lane 63 of slot 0 + lanes 0, 1 of slot 1
+    ("t10x7", 131, 7, 2, 2, 2, 0, 4, False, 10),     # 70
+    ("t2x33", 131, 33, 2, 2, 2, 0, 4, False, 2),     # 66: a trial wider than half a wave
+    ("t26x5", 131, 5, 2, 2, 2, 0, 4, False, 26),     # 130: three slots
+    ("t3x65", 70, 65, 2, 2, 2, 1, 4, False, 3),      # 195: a trial wider than a wave
+    ("t51x5", 70, 5, 2, 2, 2, 1, 4, False, 51),      # 255
+    ("t64x4", 131, 4, 2, 2, 2, 0, 4, True, 64),      # 256: the limit
+    ("t2x128", 65, 128, 2, 2, 2, 0, 4, False, 2),    # 256 with two trials
+    ("t100x1", 70, 1, 3, 3, 2, 1, 5, False, 100),    # K_trial = 1: hat_Z = 1 + 1e-50 everywhere
+]
+
+
 def make_reduced(K=3, S=3, d=2, covmode=1, seed=0, zero_transition=False) -> dict:
     """Point-estimate reduced HMMs for the VHEM sibling (hem_hmm_bwd_fwd_mex.c):
     Dirichlet rows for A and prior, means in [0, 5]^d, SPD covariances

@@ -86,6 +86,9 @@ void plancheck_resp(int K, int KT, int S, int SB, int vhem, int fold, int generi
   for (int k = 0; k < 5; ++k) out[k] = v[k];
 }
 
+// the LDS a workgroup may ask for (estep_fused_checked refuses a resp_lds above it)
+long long plancheck_lds_limit() { return (long long)kLdsLimit; }
+
 namespace {
 // out [16]: ok kernel (GatedStats) NTW G KSM NXR LG SM PER PB lds cap nzero stats_slabs
 // exact_first, then the blocks along x that the launcher asks for
