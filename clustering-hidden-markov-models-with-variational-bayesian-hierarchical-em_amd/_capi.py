@@ -185,6 +185,11 @@ EXPORTS = {
     "vbhem_em_run_trials": (_c_int, [ctypes.POINTER(BaseT), _vp, _c_int, _c_int,
                                      ctypes.POINTER(EmOptT), ctypes.POINTER(PostT), _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "vbhem_em_trials_hyp_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), _c_int, _c_int,
+                                                      _c_int, _c_int, _c_int]),
+    "vbhem_em_run_trials_hyp": (_c_int, [ctypes.POINTER(BaseT), _vp, _c_int, _c_int,
+                                         ctypes.POINTER(EmOptT), _vp, ctypes.POINTER(PostT), _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "vbhem_em_lower_bound_derivs": (_c_int, [ctypes.POINTER(PostT), ctypes.POINTER(EmOptT), _vp,
                                              _vp, _vp, _vp, _vp]),
     "vbhem_hmms_to_h3m": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int] + [_vp] * 15),

@@ -28,6 +28,13 @@ h3m.gmmnew_init_batch), or 'auto'
 The EM of the trials (opt['em_engine']): 'host' (the default) batches the E-step and
 runs the rest of an iteration in numpy, trial by trial; 'device' keeps the whole loop
 of a chunk of trials on the GPU (native_em.run_trials).
+
+The hyperparameter learning of the unique trials (opt['hyp_engine'], with learn_hyps):
+'host' (the default) runs one trial's L-BFGS after another, every evaluation an EM run of
+one trial; 'device' advances all of them in lockstep, every round of evaluations one
+batched device-side run with per-trial hyperparameters and the bound's derivatives on the
+GPU (hyp.vbhem_h3m_c_hyp_batch; one rank, K <= 256, Sb <= S <= 16,
+d <= 16 -- other shapes take the host loop).
 """
 from __future__ import annotations
 
@@ -98,8 +105,13 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     em_engine = opt.get("em_engine", "host")
     if em_engine not in ("host", "device"):
         raise ValueError(f"em_engine {em_engine!r}: 'host' or 'device'")
+    # hyp_engine='device' (with learn_hyps): every unique trial's hyperparameter learner in
+    # one batched run per round of evaluations; the default 'host' one trial after another
+    hyp_engine = opt.get("hyp_engine", "host")
+    if hyp_engine not in ("host", "device"):
+        raise ValueError(f"hyp_engine {hyp_engine!r}: 'host' or 'device'")
     if batched:
-        init_batch = wtkmeans_init_batch if initmode == "wtkmeans" else gmmnew_init_batch
+        init_batch =wtkmeans_init_batch if initmode == "wtkmeans" else gmmnew_init_batch
         posts = init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
     pts = wtkmeans_points(base, opt.get("initopt_mode", "r0")) if initmode == "wtkmeans" and not batched else None
     if initmode == "gmmNew" and not batched:
@@ -143,13 +155,20 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     if learn:
         from . import hyp
         uniq = unique_ll(LLall, 2 * opt["minDiff"] * 10)
-        one = make(base, K, S, opt["tau"], trials=1)
         hyp_info = {}
         # vbhem_h3m_c.m:102-105: every bound is invalidated; only the re-optimised
         # unique trials get one back (:157), so only they can be chosen
         LLall = np.full_like(LLall, np.nan)
-        for q in uniq:
-            h = hyp.vbhem_h3m_c_hyp(base, opt, results[q].post, one)
+        # hyp_engine='device': the unique trials' minimisers advance in lockstep, every
+        # round of evaluations one batched device-side run (hyp.vbhem_h3m_c_hyp_batch); the
+        # shapes without that loop, and an engine_factory's engine, take the host loop
+        if hyp_engine == "device" and engine_factory is None and hyp.hyp_batch_supported(base, K, S):
+            ev = hyp.device_evaluator(base, K, S, opt["tau"], torch.device(device))
+            hs = hyp.vbhem_h3m_c_hyp_batch(base, opt, [results[q].post for q in uniq], ev)
+        else:
+            one = make(base, K, S, opt["tau"], trials=1)
+            hs = [hyp.vbhem_h3m_c_hyp(base, opt, results[q].post, one) for q in uniq]
+        for q, h in zip(uniq, hs):
             results[q] = h["result"]
             LLall[q] = h["result"].LL
             hyp_info[q] = h

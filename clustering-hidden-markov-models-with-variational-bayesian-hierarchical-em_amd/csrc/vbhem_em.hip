@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "vbhem_em.h"
+#include "vbhem_em_deriv_terms.h"
 #include "vbhem_em_dev.h"
 #include "vbhem_em_trial_ctrl.h"
 #include "vbhem_internal.h"
@@ -729,14 +730,14 @@ size_t post_len(int K, int S, int d, size_t dd) {
   return (size_t)K + 3 * (size_t)K * S + (size_t)K * S * S + (size_t)K * S * d + (size_t)K * S * dd;
 }
 
-// the doubles of vbhem_em_run_trials' workspace after the E-step's own
-size_t trials_ws_doubles(int N, int K, int S, int d, size_t dd, int R, size_t slen) {
-  const size_t KS = (size_t)K * S;
+// the doubles of the trials loop's workspace after the E-step's own; nW: the W0
+// entries the derivatives are laid out for
+size_t trials_ws_doubles(int N, int K, int S, int d, size_t dd, int R, size_t slen, int nW) {
+  const size_t KS = (size_t)K * S, nd = (size_t)VBHEM_DLL_LEN(d, nW);
   const size_t consts = KS * S + KS + KS * d + KS * dd + KS + (size_t)K;
   return (size_t)R * (2 * consts + 2 * post_len(K, S, d, dd) + 2 * KS + KS * 13 + 2 * slen +
-                      2 * (size_t)N * K) +
-         (size_t)d + (size_t)d * d + ((size_t)R * sizeof(vbhem::TrialCtrl) + 7) / 8 +
-         ((size_t)R * sizeof(int) + 7) / 8;
+                      2 * (size_t)N * K + (size_t)vbhem::hyp_table_len(d) + nd * KS + nd) +
+         ((size_t)R * sizeof(vbhem::TrialCtrl) + 7) / 8 + ((size_t)R * sizeof(int) + 7) / 8;
 }
 
 // why a shape is outside vbhem_em_run_trials (nullptr: supported)
@@ -910,37 +911,58 @@ int vbhem_em_run(const vbhem_base_t *base, const double *tildeN_dev, int T,
                           allreduce_ctx, nullptr);
 }
 
-size_t vbhem_em_trials_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T) {
+size_t vbhem_em_trials_hyp_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T,
+                                           int W0_len) {
   if (!base || trials_unsupported(base, KT, S, R)) return 0;
   const int d = base->d;
+  if (W0_len != 1 && W0_len != d) return 0;
   const size_t dd = base->covmode == VBHEM_COV_FULL ? (size_t)d * d : (size_t)d;
   vbhem_cluster_t c = {R * KT, S, nullptr, nullptr, nullptr, nullptr, nullptr};
   const size_t fused = vbhem_fused_trials_workspace_bytes(base, &c, R, T);
   if (fused == 0) return 0;
   const size_t slen = vbhem_stats_len(KT, S, d, base->covmode);
   return (fused + 255) / 256 * 256 +
-         trials_ws_doubles(base->N, KT, S, d, dd, R, slen) * sizeof(double) + 256;
+         trials_ws_doubles(base->N, KT, S, d, dd, R, slen, W0_len) * sizeof(double) + 256;
 }
 
-int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
-                        const vbhem_em_opt_t *opt, vbhem_post_t *posts, double *LogLs, int *iters,
-                        double *L_final, int *stable, double *stats_out, double *hatZ_dev,
-                        double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-  if (!base || !posts || R < 1 || !post_ok(&posts[0]) || !opt_ok(opt, posts[0].d) || !LogLs ||
-      !iters || !L_final || !stable || !stats_out || !hatZ_dev || !LL_dev || !tildeN_dev)
-    return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: null or invalid argument");
+size_t vbhem_em_trials_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T) {
+  // whatever W0 the run is given: the longer of the two layouts
+  return base ? vbhem_em_trials_hyp_workspace_bytes(base, KT, S, R, T, base->d) : 0;
+}
+
+// The trials loop behind vbhem_em_run_trials (every opts[r] the same one, no mask, no
+// derivatives) and vbhem_em_run_trials_hyp; `fn` names the entry in error texts.
+static int run_trials_impl(const char *fn, const vbhem_base_t *base, const double *tildeN_dev, int R,
+                           int T, const vbhem_em_opt_t *const *opts, const int *active,
+                           vbhem_post_t *posts, double *LogLs, int *iters, double *L_final,
+                           int *stable, double *stats_out, double *hatZ_dev, double *LL_dev,
+                           double *dLL, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  const std::string who = std::string(fn) + ": ";
+  if (!base || !posts || R < 1 || !post_ok(&posts[0]) || !opts || !opt_ok(opts[0], posts[0].d) ||
+      !LogLs || !iters || !L_final || !stable || !stats_out || !hatZ_dev || !LL_dev || !tildeN_dev)
+    return vbhem::set_error(VBHEM_ERR_ARG, who + "null or invalid argument");
+  const vbhem_em_opt_t *opt = opts[0];
   const int K = posts[0].K, S = posts[0].S, d = posts[0].d, cov = posts[0].covmode;
   if (d != base->d || cov != base->covmode)
-    return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: d / covmode differ from the base set's");
+    return vbhem::set_error(VBHEM_ERR_ARG, who + "d / covmode differ from the base set's");
+  for (int r = 1; r < R; ++r) {
+    if (!opt_ok(opts[r], d)) return vbhem::set_error(VBHEM_ERR_ARG, who + "null or invalid argument");
+    if (opts[r]->max_iter != opt->max_iter || opts[r]->minDiff != opt->minDiff ||
+        opts[r]->Nv != opt->Nv || opts[r]->W0_len != opt->W0_len)
+      return vbhem::set_error(VBHEM_ERR_ARG,
+                              who + "max_iter, minDiff, Nv and W0_len must be equal in every trial's options");
+  }
   if (const char *why = trials_unsupported(base, K, S, R))
-    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, std::string("vbhem_em_run_trials: ") + why);
+    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, who + why);
   for (int r = 1; r < R; ++r)
     if (!post_ok(&posts[r]) || posts[r].K != K || posts[r].S != S || posts[r].d != d ||
         posts[r].covmode != cov)
-      return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials: the trials' posteriors differ in shape");
-  const size_t need = vbhem_em_trials_workspace_bytes(base, K, S, R, T);
+      return vbhem::set_error(VBHEM_ERR_ARG, who + "the trials' posteriors differ in shape");
+  const int nW = opt->W0_len, nd = VBHEM_DLL_LEN(d, nW);
+  // (at most what vbhem_em_trials_workspace_bytes asks for: the layout below is this one)
+  const size_t need = vbhem_em_trials_hyp_workspace_bytes(base, K, S, R, T, nW);
   if (need == 0)
-    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, "vbhem_em_run_trials: no batched E-step for this shape");
+    return vbhem::set_error(VBHEM_ERR_UNSUPPORTED, who + "no batched E-step for this shape");
   if (!workspace_dev || workspace_bytes < need) return VBHEM_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int N = base->N, RK = R * K;
@@ -962,8 +984,10 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
   double *dstats_out = p; p += (size_t)R * slen;
   double *dhz = p; p += (size_t)N * RK;
   double *dll = p; p += (size_t)N * RK;
-  double *dm0 = p; p += d;
-  double *dW0inv = p; p += (size_t)d * d;
+  const size_t hlen = (size_t)vbhem::hyp_table_len(d);
+  double *dhyp = p; p += (size_t)R * hlen;
+  double *dterms = p; p += (size_t)R * nd * KS;
+  double *ddLL = p; p += (size_t)R * nd;
   vbhem::TrialCtrl *dctrl = reinterpret_cast<vbhem::TrialCtrl *>(p);
   p += ((size_t)R * sizeof(vbhem::TrialCtrl) + 7) / 8;
   int *dticket = reinterpret_cast<int *>(p);
@@ -971,17 +995,31 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
                         dc + R * (nA + nPi + nm + nP)};
   double *dlogOmega = dc + R * (nA + nPi + nm + nP + nc);
 
-  std::vector<double> W0inv;
-  w0_inv(opt, d, W0inv);
+  // every trial's hyperparameter table (vbhem_em_deriv_terms.h), once per call: the
+  // five scalars, the bound's constants, m0 and W0^-1 of its own options
+  std::vector<double> hyp((size_t)R * hlen), W0inv;
+  for (int r = 0; r < R; ++r) {
+    const vbhem_em_opt_t *o = opts[r];
+    double *h = hyp.data() + (size_t)r * hlen;
+    if (r > 0 && o == opts[r - 1]) {  // the same options: the same table
+      std::copy(h - hlen, h, h);
+      continue;
+    }
+    w0_inv(o, d, W0inv);
+    h[vbhem::kHypAlpha0] = o->alpha0; h[vbhem::kHypEta0] = o->eta0;
+    h[vbhem::kHypEpsilon0] = o->epsilon0; h[vbhem::kHypLambda0] = o->lambda0;
+    h[vbhem::kHypV0] = o->v0;
+    bound_constants(o, K, S, d, W0inv, h[vbhem::kHypLogCalpha0], h[vbhem::kHypLogCeta0],
+                    h[vbhem::kHypLogCepsilon0], h[vbhem::kHypLogB0]);
+    std::copy(o->m0, o->m0 + d, h + vbhem::kHypM0);
+    std::copy(W0inv.begin(), W0inv.end(), h + vbhem::kHypM0 + d);
+  }
   const int ldL = opt->max_iter + 1;
   vbhem::EmTrialsArgs t{};
   vbhem::EmDevArgs &a = t.a;
   a.K = K; a.S = S; a.d = d; a.covmode = cov; a.NU = (int)vbhem_stats_nu(d, cov);
   a.stats = dstats;
-  a.alpha0 = opt->alpha0; a.eta0 = opt->eta0; a.epsilon0 = opt->epsilon0; a.lambda0 = opt->lambda0;
-  a.v0 = opt->v0;
-  bound_constants(opt, K, S, d, W0inv, a.logCalpha0, a.logCeta0, a.logCepsilon0, a.logB0);
-  a.m0 = dm0; a.W0inv = dW0inv;
+  t.hyp = dhyp; t.hyp_stride = hlen; t.W0_len = nW; t.dterms = dterms; t.dLL = ddLL;
   a.logA = dc; a.logPi = dc + R * nA; a.cm = dc + R * (nA + nPi); a.P = dc + R * (nA + nPi + nm);
   a.c = dc + R * (nA + nPi + nm + nP); a.lLT = dlLT;
   a.logOmega = dlogOmega; a.logdetW = dlogdetW; a.part = dpart;
@@ -998,18 +1036,32 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
 
   // the initial posteriors, packed as buffer 0 of every trial, and the records
   std::vector<double> hp(2 * (size_t)R * postn);
-  const size_t fn[7] = {(size_t)K, KS, KS * S, KS, KS, KS * d, KS * dd};
+  const size_t pn[7] = {(size_t)K, KS, KS * S, KS, KS, KS * d, KS * dd};
   for (int r = 0; r < R; ++r) {
     const double *src[7] = {posts[r].alpha, posts[r].eta, posts[r].epsilon, posts[r].lam,
                             posts[r].v, posts[r].m, posts[r].W};
     double *q = hp.data() + (size_t)r * postn;
     for (int x = 0; x < 7; ++x) {
-      std::copy(src[x], src[x] + fn[x], q);
-      q += fn[x];
+      std::copy(src[x], src[x] + pn[x], q);
+      q += pn[x];
     }
   }
   std::vector<vbhem::TrialCtrl> ctrl((size_t)R);
   for (int r = 0; r < R; ++r) vbhem::trial_ctrl_init(&ctrl[(size_t)r]);
+  // An inactive slot is frozen from the start, but only AFTER the prelude launch (a done
+  // trial's waves leave before the prelude): its clusters ride along in every E-step,
+  // whose emission GEMM shifts by the mean of all clusters' means, so its constants must
+  // be those of its (finite) posterior.  stop_iter = -2: no latch ever takes it for a
+  // trial that stopped at its iteration (the first latch runs with j = -1).
+  std::vector<vbhem::TrialCtrl> frozen;
+  if (active) {
+    frozen = ctrl;
+    for (int r = 0; r < R; ++r)
+      if (!active[r]) {
+        frozen[(size_t)r].done = 1;
+        frozen[(size_t)r].stop_iter = -2;
+      }
+  }
   // mapped host memory: flag[2] | active[2] | (64 bytes in) the bounds [R][max_iter + 1]
   MappedBuf mb;
   const size_t nL = (size_t)R * ldL;
@@ -1024,15 +1076,19 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
     t.active = t.flag + 2;
     t.LogLs = reinterpret_cast<double *>(mb.d + 64);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(dm0, opt->m0, d * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(dW0inv, W0inv.data(), W0inv.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(dhyp, hyp.data(), hyp.size() * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess)
     e = hipMemcpyAsync(dposts, hp.data(), (size_t)R * postn * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess)
     e = hipMemcpyAsync(dctrl, ctrl.data(), ctrl.size() * sizeof(vbhem::TrialCtrl), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(dticket, 0, (size_t)R * sizeof(int), st);
   if (e == hipSuccess) e = vbhem::launch_em_trials(t, vbhem::kEmPrelude, st);
+  if (e == hipSuccess && active) {
+    e = hipMemcpyAsync(dctrl, frozen.data(), frozen.size() * sizeof(vbhem::TrialCtrl), hipMemcpyHostToDevice, st);
+    // nothing is latched for an inactive slot: its statistics come back as zeros
+    if (e == hipSuccess) e = hipMemsetAsync(dstats_out, 0, (size_t)R * slen * sizeof(double), st);
+  }
   if (e == hipSuccess) e = vbhem::launch_trials_latch(t, -1, st);
   int rc = VBHEM_OK;
   // iteration j: the E-step of all R K clusters, every running trial's bound + M-step
@@ -1061,6 +1117,15 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
   }
   hipError_t e2 = hipStreamSynchronize(st);  // the iteration queued ahead drains
   if (e == hipSuccess) e = e2;
+  // the derivatives of every stable trial's last bound, at the posterior before its last
+  // M-step (its other buffer; the iteration queued ahead changed nothing of a done trial)
+  std::vector<double> hdLL;
+  if (e == hipSuccess && rc == VBHEM_OK && finished && dLL) {
+    hdLL.resize((size_t)R * nd);
+    e = vbhem::launch_trials_derivs(t, st);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(hdLL.data(), ddLL, hdLL.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  }
   if (e == hipSuccess && rc == VBHEM_OK)
     e = hipMemcpyAsync(hp.data(), dposts, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && rc == VBHEM_OK)
@@ -1071,23 +1136,53 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
   if (e == hipSuccess && rc == VBHEM_OK) std::copy(L_h, L_h + nL, LogLs);
   if (e == hipSuccess) release_mapped_buf(mb);  // a failed stream may still write it: not reused
   if (rc != VBHEM_OK) return rc;
-  if (e != hipSuccess) return vbhem::hip_fail(e, "vbhem_em_run_trials");
+  if (e != hipSuccess) return vbhem::hip_fail(e, fn);
   if (!finished)
-    return vbhem::set_error(VBHEM_ERR_HIP, "vbhem_em_run_trials: trials still running after max_iter + 1 iterations");
+    return vbhem::set_error(VBHEM_ERR_HIP, who + "trials still running after max_iter + 1 iterations");
   for (int r = 0; r < R; ++r) {
     const vbhem::TrialCtrl &c = ctrl[(size_t)r];
+    const bool on = !active || active[r];
     iters[r] = c.it;
     L_final[r] = c.L_final;
-    stable[r] = c.stable;
+    stable[r] = on ? c.stable : 0;
     double *dst[7] = {posts[r].alpha, posts[r].eta, posts[r].epsilon, posts[r].lam,
                       posts[r].v, posts[r].m, posts[r].W};
     const double *q = hp.data() + ((size_t)c.cur * R + r) * postn;
     for (int x = 0; x < 7; ++x) {
-      std::copy(q, q + fn[x], dst[x]);
-      q += fn[x];
+      std::copy(q, q + pn[x], dst[x]);
+      q += pn[x];
+    }
+    if (dLL) {
+      double *g = dLL + (size_t)r * nd;
+      if (on && c.stable && c.it >= 1) std::copy(hdLL.begin() + (size_t)r * nd, hdLL.begin() + (size_t)(r + 1) * nd, g);
+      else std::fill(g, g + nd, std::nan(""));
     }
   }
   return VBHEM_OK;
+}
+
+int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
+                        const vbhem_em_opt_t *opt, vbhem_post_t *posts, double *LogLs, int *iters,
+                        double *L_final, int *stable, double *stats_out, double *hatZ_dev,
+                        double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  const std::vector<const vbhem_em_opt_t *> opts((size_t)(R > 0 ? R : 1), opt);
+  return run_trials_impl("vbhem_em_run_trials", base, tildeN_dev, R, T, opts.data(), nullptr, posts,
+                         LogLs, iters, L_final, stable, stats_out, hatZ_dev, LL_dev, nullptr,
+                         workspace_dev, workspace_bytes, stream);
+}
+
+int vbhem_em_run_trials_hyp(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
+                            const vbhem_em_opt_t *opts, const int *active, vbhem_post_t *posts,
+                            double *LogLs, int *iters, double *L_final, int *stable,
+                            double *stats_out, double *hatZ_dev, double *LL_dev, double *dLL,
+                            void *workspace_dev, size_t workspace_bytes, void *stream) {
+  if (!opts || R < 1)
+    return vbhem::set_error(VBHEM_ERR_ARG, "vbhem_em_run_trials_hyp: null or invalid argument");
+  std::vector<const vbhem_em_opt_t *> po((size_t)R);
+  for (int r = 0; r < R; ++r) po[(size_t)r] = opts + r;
+  return run_trials_impl("vbhem_em_run_trials_hyp", base, tildeN_dev, R, T, po.data(), active, posts,
+                         LogLs, iters, L_final, stable, stats_out, hatZ_dev, LL_dev, dLL,
+                         workspace_dev, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -64,6 +64,15 @@ struct EmTrialsArgs {
   double *hz_out, *ll_out;          // [N][R K]
   double *stats_out;                // [R][stats_len]
   int *flag, *active;               // [2] each (mapped host memory), slot j % 2
+  // the hyperparameters, per trial: trial r's table (vbhem_em_deriv_terms.h: the five
+  // scalars, the bound's four constants, m0, W0^-1) lies at hyp + r hyp_stride; the
+  // kernels read them from there, a.alpha0 .. a.W0inv are not used
+  const double *hyp;
+  size_t hyp_stride;
+  // the bound's derivatives (launch_trials_derivs): W0 entries, the per-(k, s) terms
+  // [R][5 + W0_len + d][K S] and the result [R][5 + W0_len + d] (device)
+  int W0_len;
+  double *dterms, *dLL;
 };
 
 // kEmPrelude: the prelude of every trial's buffer 0.  kEmIterate: for every trial
@@ -75,5 +84,10 @@ hipError_t launch_em_trials(const EmTrialsArgs &t, int mode, hipStream_t st);
 // running trial and puts back those of a trial whose bound was NaN, then writes
 // active[j % 2] = trials not done and flag[j % 2] = j + 1.
 hipError_t launch_trials_latch(const EmTrialsArgs &t, int j, hipStream_t st);
+// After the loop (every trial done): the raw derivatives of every stable trial's last
+// accepted bound (vbhemh3m_lb.m:202-345), at the posterior before its last M-step
+// (buffer cur ^ 1), into dLL.  A trial that is unstable or took no iteration is left
+// alone (the caller writes its NaN).  vbhem_em_trials_derivs.hip.
+hipError_t launch_trials_derivs(const EmTrialsArgs &t, hipStream_t st);
 
 }  // namespace vbhem

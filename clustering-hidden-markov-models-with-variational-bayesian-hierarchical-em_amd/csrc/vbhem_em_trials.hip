@@ -10,7 +10,9 @@
 // em_iter_kernel, vbhem_em_dev.hip) on pointers that address its trial: the
 // statistics at stats + r stats_len, the posterior buffer ctrl[r].cur, the M-step
 // into the trial's other buffer, the prelude into the trial's slices of the
-// trial-major cluster constants and of logOmega.  The last wave of a trial to
+// trial-major cluster constants and of logOmega, and the trial's OWN hyperparameters
+// (its table at hyp + r hyp_stride, vbhem_em_deriv_terms.h; vbhem_em_run_trials fills
+// R copies of one, vbhem_em_run_trials_hyp one per trial).  The last wave of a trial to
 // finish (a ticket per trial) sums that trial's K S partials in em_iter_kernel's
 // order, forms the bound and runs trial_ctrl_step (vbhem_em_trial_ctrl.h): record
 // the bound, accept the M-step (flip cur), or stop.  The waves of a trial whose
@@ -30,6 +32,7 @@
 
 #include <cmath>
 
+#include "vbhem_em_deriv_terms.h"
 #include "vbhem_em_dev.h"
 #include "vbhem_em_iter_body.h"
 #include "vbhem_em_trial_ctrl.h"
@@ -68,6 +71,13 @@ __global__ __launch_bounds__(64 * kWaves) void em_iter_trials_kernel(const EmTri
   a.c = t.a.c + (size_t)r * KS; a.lLT = t.a.lLT + (size_t)r * KS;
   a.logOmega = t.a.logOmega + (size_t)r * K; a.logdetW = t.a.logdetW + (size_t)r * KS;
   a.part = t.a.part + (size_t)r * kNQ * KS;
+  // ... and its own hyperparameters (wave-uniform reads of the trial's table)
+  const double *h = t.hyp + (size_t)r * t.hyp_stride;
+  a.alpha0 = h[kHypAlpha0]; a.eta0 = h[kHypEta0]; a.epsilon0 = h[kHypEpsilon0];
+  a.lambda0 = h[kHypLambda0]; a.v0 = h[kHypV0];
+  a.logCalpha0 = h[kHypLogCalpha0]; a.logCeta0 = h[kHypLogCeta0];
+  a.logCepsilon0 = h[kHypLogCepsilon0]; a.logB0 = h[kHypLogB0];
+  a.m0 = h + kHypM0; a.W0inv = h + kHypM0 + d;
   const StatsView st(a.stats, K, S);
   em_ks_body(a, iterate, ks, lane, glds[wave], st);
 
@@ -146,7 +156,7 @@ __global__ __launch_bounds__(kLatchThreads) void trials_latch_kernel(const EmTri
 
 hipError_t launch_em_trials(const EmTrialsArgs &t, int mode, hipStream_t st) {
   if (!em_dev_supported(t.a.d, t.a.S) || t.R < 1 || !t.ctrl || !t.ticket || !t.LogLs || !t.a.part ||
-      t.ldL < t.max_iter + 1)
+      !t.hyp || t.hyp_stride < (size_t)hyp_table_len(t.a.d) || t.ldL < t.max_iter + 1)
     return hipErrorInvalidValue;
   const int nw = t.R * t.a.K * t.a.S;
   hipLaunchKernelGGL(em_iter_trials_kernel, dim3((nw + kWaves - 1) / kWaves), dim3(64 * kWaves), 0,

@@ -137,12 +137,14 @@ class TrialsResult:
     results: List[EMResult]         # one per trial (vbhem_h3m_c.m: h3m_news)
     LLall: np.ndarray               # [R] final lower bound per trial (LLall)
     best: int                       # argmax LLall (vbhem_h3m_c.m:167-170)
+    raw: Optional[dict] = None      # native_em.run_trials: what the C entry wrote, slot by slot
 
 
 def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *,
                        total_N: Optional[int] = None,
                        allreduce: Optional[Callable[[torch.Tensor], None]] = None,
-                       max_iter: Optional[int] = None, em_engine: str = "host") -> TrialsResult:
+                       max_iter: Optional[int] = None, em_engine: str = "host",
+                       opts: Optional[List[dict]] = None, active=None) -> TrialsResult:
     """R EM trials from their own initial posteriors (vbhem_h3m_c.m:28-67,
     `parfor it = 1:numits`), run in lockstep with one batched E-step launch per
     iteration (vbhem_estep_fused_trials).  Every trial follows
@@ -153,7 +155,15 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
     em_engine: ``"host"`` (the default) runs the bound, the M-step, the prelude
     and the stopping rule of every trial in numpy between two launches;
     ``"device"`` runs them on the GPU as well (:func:`vbhem_amd.native_em.run_trials`:
-    one rank, a device :class:`EStepEngine`, R K <= 256, Sb <= S <= 16, d <= 16)."""
+    one rank, a device :class:`EStepEngine`, R K <= 256, Sb <= S <= 16, d <= 16).
+
+    opts: one options dict per trial (default: ``opt`` for all): each trial's bound,
+    M-step and, with its ``calc_LLderiv``, derivatives (``res.dLL``) under its own
+    hyperparameters, exactly as :func:`vbhem_h3m_c_step_fc` with those options;
+    ``max_iter``, ``minDiff`` and ``Nv`` are taken from the first.  active: a flag per
+    trial; a slot whose flag is false is never iterated (its clusters ride along in the
+    launches with the constants of its posterior, which must be finite), its result is
+    ``None`` and its bound NaN; ``best`` is taken over the active trials."""
     if em_engine not in ("host", "device"):
         raise ValueError(f"em_engine {em_engine!r}: 'host' or 'device'")
     if em_engine == "device":
@@ -162,8 +172,20 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
         if not isinstance(engine, EStepEngine):
             raise ValueError("em_engine='device' needs a device EStepEngine")
         from . import native_em
-        return native_em.run_trials(posts, engine, opt, max_iter, total_N=total_N)
+        if opts is None and active is None:
+            return native_em.run_trials(posts, engine, opt, max_iter, total_N=total_N)
+        deriv = any(bool(o.get("calc_LLderiv", 0)) for o in (opts or [opt]))
+        return native_em.run_trials(posts, engine, opt, max_iter, total_N=total_N, opts=opts,
+                                    active=active, calc_deriv=deriv)
     R = len(posts)
+    if opts is not None:
+        if len(opts) != R:
+            raise ValueError("opts must hold one options dict per trial")
+        opt = opts[0]
+    ropt = [opt] * R if opts is None else list(opts)
+    act = [True] * R if active is None else [bool(x) for x in active]
+    if len(act) != R:
+        raise ValueError("active must hold one flag per trial")
     if engine.trials != R:
         raise ValueError("engine.trials must equal len(posts)")
     covmode = engine.base.covmode
@@ -181,7 +203,8 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
     stable = [True] * R
     L = [-np.inf] * R
     Nj = [np.zeros(K) for _ in range(R)]
-    done = [False] * R
+    done = [not x for x in act]
+    dLL: List[Optional[dict]] = [None] * R
     hatZ: List[Optional[torch.Tensor]] = [None] * R
     Lel: List[Optional[torch.Tensor]] = [None] * R
     consts = [host.cluster_constants(p, covmode) for p in post]
@@ -195,9 +218,17 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
                 continue
             st = host.unpack_stats(vec[r * SL:(r + 1) * SL], K, S, d, covmode)
             Nj[r] = st["Nj"] + 1e-50
-            Lr = host.lower_bound(st["Lt1"], st["Lt7"], Nj[r], logOm[r], post[r], consts[r], opt,
+            Lr = host.lower_bound(st["Lt1"], st["Lt7"], Nj[r], logOm[r], post[r], consts[r], ropt[r],
                                   covmode)
             stop = (it[r] > 1 and abs((Lr - lastL[r]) / lastL[r]) <= minDiff) or it[r] == maxIter
+            do_deriv = bool(ropt[r].get("calc_LLderiv", 0))
+            if (stop or np.isnan(Lr)) and do_deriv:
+                # step_fc.m:356-368: before the last M-step; invalidated when unstable
+                dLL[r] = host.lower_bound_derivs(logOm[r], post[r], consts[r], ropt[r], covmode,
+                                                 ropt[r].get("hyp_clipped"))
+                if np.isnan(Lr):
+                    dLL[r] = {k: np.full_like(np.atleast_1d(v), np.nan) for k, v in dLL[r].items()
+                              if k != "raw"}
             if np.isnan(Lr):  # step_fc.m:338-374
                 L[r] = -np.inf
                 stable[r] = False
@@ -205,7 +236,7 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
             else:
                 L[r] = Lr
                 syn[r] = host.finish_statistics(st, covmode)
-                post[r] = host.mstep(syn[r], Nj[r], opt, covmode, post[r].W0mode)
+                post[r] = host.mstep(syn[r], Nj[r], ropt[r], covmode, post[r].W0mode)
                 it[r] += 1
                 LogLs[r].append(Lr)
                 lastL[r] = Lr
@@ -219,11 +250,15 @@ def vbhem_h3m_c_trials(posts: List[Posterior], engine: EStepEngine, opt: dict, *
                 logOm[r] = host.log_omega_tilde(post[r].alpha)
     results = []
     for r in range(R):
+        if not act[r]:
+            results.append(None)
+            continue
         res = EMResult(post=post[r], LogLs=LogLs[r], LL=L[r], iters=it[r], stable=stable[r],
-                       hatZ=hatZ[r], L_elbo=Lel[r], Nj=Nj[r], syn=syn[r])
+                       hatZ=hatZ[r], L_elbo=Lel[r], Nj=Nj[r], syn=syn[r], dLL=dLL[r])
         if stable[r]:
             res.point = host.convert_to_point(post[r], covmode)
             res.label = torch.argmax(res.hatZ, dim=1)
         results.append(res)
-    LLall = np.array([x.LL for x in results])
-    return TrialsResult(results=results, LLall=LLall, best=int(np.argmax(LLall)))
+    LLall = np.array([x.LL if x is not None else np.nan for x in results])
+    best = 0 if np.all(np.isnan(LLall)) else int(np.nanargmax(LLall))
+    return TrialsResult(results=results, LLall=LLall, best=best)

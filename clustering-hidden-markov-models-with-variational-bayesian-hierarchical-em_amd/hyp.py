@@ -6,6 +6,11 @@
   the trial's own posterior ('inith3m', vbhemhmm_init.m:428-455) with
   ``calc_LLderiv`` on, so the gradient is vbhemh3m_lb.m:202-356 at its last
   E-step (host.lower_bound_derivs); then one final EM run with the optimum.
+* :func:`vbhem_h3m_c_hyp_batch` -- the same for all unique trials at once
+  (vbhem_h3m_c.m:96-160 runs them in a ``parfor``): their minimisers advance in
+  lockstep (:func:`minimize_lockstep`), every round of evaluations one batched call
+  (:func:`device_evaluator`: the device-side trials loop with per-trial
+  hyperparameters and the derivatives on the GPU).
 * :func:`hypinfo` -- vbhem_get_hypinfo.m (names, transforms, derivative keys).
 * :func:`minimize` -- src/util/minimize_new.m: the LBFGS / BFGS / CG direction
   methods with the Wolfe-Powell line search (cubic extrapolation and
@@ -345,3 +350,190 @@ def vbhem_h3m_c_hyp(base: BaseSet, opt: dict, init_post: Posterior, engine: ESte
     final = em_run(init_post, engine, o2)
     return dict(result=final, opt_transhyp=Xopt, opt_L=-fX[-1], fX=fX, line_searches=nls,
                 evaluations=n_eval[0], vbopt=o2, hypinfo=info)
+
+
+# ----------------------------------------------------------------------------
+# all unique trials at once (vbhem_h3m_c.m:96-160, the reference's `parfor`)
+# ----------------------------------------------------------------------------
+class _Slot:
+    def __init__(self):
+        self.request = None     # the point the minimiser waits for (set by its thread)
+        self.reply = None       # (f, df) or an exception (set by the coordinator)
+        self.finished = False
+        self.result = None
+        self.error = None
+
+
+def minimize_lockstep(X0s, Fbatch: Callable, length: int = 100, method: str = "LBFGS",
+                      MFEPLS: int = 10, MSR: float = 100.0, mem: Optional[int] = None):
+    """One :func:`minimize` per slot, advanced in lockstep: every round gathers the
+    points the running minimisers ask for and calls ``Fbatch({slot: x})`` ONCE, which
+    returns ``{slot: (f, df)}``; a slot that has finished drops out.  Returns the list
+    of what ``minimize(X0s[q], F_q, ...)`` returns for every slot q -- the same points
+    in the same order, so the same bits: each minimiser IS :func:`minimize`, running in
+    a thread of its own that blocks inside its objective until the round's answer is
+    there.  Only the calling thread runs ``Fbatch`` (so only it touches the device).
+
+    A value of ``Fbatch``'s answer may be an exception instance: it is raised inside
+    that slot's objective alone, where the line search treats it as it treats any error
+    of the objective (minimize_new.m:147-155: bisect during extrapolation); an
+    evaluation that returns Inf / NaN bisects that slot only in the same way.  When
+    ``Fbatch`` itself raises, every slot of that round sees the exception.  An error
+    that ends a slot's ``minimize`` is raised here once every slot has stopped."""
+    import threading
+    slots = [_Slot() for _ in X0s]
+    cond = threading.Condition()
+
+    def worker(q, X0):
+        sl = slots[q]
+
+        def F(x):
+            with cond:
+                sl.request = np.array(x, dtype=float)
+                cond.notify_all()
+                while sl.reply is None:
+                    cond.wait()
+                r, sl.reply = sl.reply, None
+            if isinstance(r, BaseException):
+                raise r
+            return r
+
+        try:
+            sl.result = minimize(X0, F, length=length, method=method, MFEPLS=MFEPLS, MSR=MSR, mem=mem)
+        except BaseException as exc:  # noqa: BLE001 -- re-raised by the coordinator
+            sl.error = exc
+        finally:
+            with cond:
+                sl.finished = True
+                cond.notify_all()
+
+    threads = [threading.Thread(target=worker, args=(q, X0), daemon=True) for q, X0 in enumerate(X0s)]
+    for t in threads:
+        t.start()
+    while True:
+        with cond:
+            while not all(sl.finished or sl.request is not None for sl in slots):
+                cond.wait()
+            req = {q: sl.request for q, sl in enumerate(slots) if not sl.finished}
+        if not req:
+            break
+        try:
+            ans = Fbatch(req)
+        except Exception as exc:  # noqa: BLE001 -- handed to the slots of this round
+            ans = {q: exc for q in req}
+        with cond:
+            for q in req:
+                slots[q].request = None
+                slots[q].reply = ans[q]
+            cond.notify_all()
+    for t in threads:
+        t.join()
+    for sl in slots:
+        if sl.error is not None:
+            raise sl.error
+    return [sl.result for sl in slots]
+
+
+def host_evaluator(make_engine: Callable) -> Callable:
+    """``evaluate(posts, opts, active, calc_deriv)`` of :func:`vbhem_h3m_c_hyp_batch` on
+    the host engine of the trials (em.vbhem_h3m_c_trials with per-trial options);
+    ``make_engine(R)`` builds the E-step engine of R trials (kept per R)."""
+    engines = {}
+
+    def evaluate(posts, opts, active, calc_deriv):
+        R = len(posts)
+        if R not in engines:
+            engines[R] = make_engine(R)
+        o = [dict(x, calc_LLderiv=1 if calc_deriv else 0) for x in opts]
+        return em.vbhem_h3m_c_trials(posts, engines[R], o[0], opts=o, active=active).results
+
+    return evaluate
+
+
+def device_evaluator(base: BaseSet, K: int, S: int, T: int, device="cuda") -> Callable:
+    """``evaluate`` on the device-side trials loop (native_em.run_trials: the EM of every
+    slot and the derivatives of its last bound in one batched run); one
+    ``EStepEngine(base, R K, S, T, trials=R)`` per number of slots R."""
+    engines = {}
+
+    def evaluate(posts, opts, active, calc_deriv):
+        from . import native_em
+        R = len(posts)
+        if R not in engines:
+            engines[R] = EStepEngine(base, R * K, S, T, device=device, trials=R)
+        return native_em.run_trials(posts, engines[R], opts[0], opts=opts, active=active,
+                                    calc_deriv=calc_deriv).results
+
+    return evaluate
+
+
+def hyp_batch_supported(base: BaseSet, K: int, S: int) -> bool:
+    """The shapes of the device-side trials loop (one slot at least)."""
+    return K <= 256 and base.SB <= S <= 16 and base.d <= 16
+
+
+def vbhem_h3m_c_hyp_batch(base: BaseSet, opt: dict, init_posts: List[Posterior], evaluate: Callable,
+                          length: Optional[int] = None, learn_hyps=None) -> List[dict]:
+    """:func:`vbhem_h3m_c_hyp` for several trials at once: their minimisers advance in
+    lockstep (:func:`minimize_lockstep`), so every round of objective evaluations -- an
+    EM run from each slot's own posterior under its own hyperparameters, with the
+    derivatives of its last bound -- is ONE call ``evaluate(posts, opts, active,
+    calc_deriv) -> [EMResult or None]`` (:func:`device_evaluator`,
+    :func:`host_evaluator`); slots that wait for nothing in a round are inactive in it.
+    The final EM runs with every slot's optimum are one more call.  At most
+    ``256 // K`` slots go into one call; more trials run in chunks, one after another.
+
+    Returns per trial the dict of :func:`vbhem_h3m_c_hyp`, plus every evaluated point of
+    its minimiser and what came back: ``X_evals``, ``f_evals``, ``g_evals`` (the
+    objective -LL and its gradient; NaN where the evaluation raised)."""
+    info = hypinfo(opt.get("learn_hyps", 1) if learn_hyps is None else learn_hyps, opt)
+    methods = {"minimize-lbfgs": "LBFGS", "minimize-bfgs": "BFGS", "minimize-cg": "CG"}
+    name = opt.get("minimizer", "minimize-lbfgs")
+    if name not in methods:                              # vbhem_h3m_c_hyp.m:51-52
+        raise ValueError("bad minimizer specified")
+    K = init_posts[0].m.shape[0] if init_posts else 1
+    per = max(1, 256 // K)
+    X0 = init_x(opt, info)
+    n = int(length or opt.get("hyp_length", 100))
+    out: List[dict] = []
+    for c0 in range(0, len(init_posts), per):
+        posts = list(init_posts[c0:c0 + per])
+        Q = len(posts)
+        rec = [dict(X=[], f=[], g=[]) for _ in range(Q)]
+
+        def Fbatch(req, posts=posts, Q=Q, rec=rec):
+            opts = [None] * Q
+            for q, X in req.items():
+                o = set_opt(X, opt, info)
+                o, flags = clip_hyps(o, with_flags=True)  # vbh3m_grad: vbhem_clip_hyps
+                o["hyp_clipped"] = flags
+                o["calc_LLderiv"] = 1
+                opts[q] = o
+            filler = opts[next(iter(req))]                # an inactive slot: any valid options
+            active = [o is not None for o in opts]
+            try:
+                res = evaluate(posts, [o if o is not None else filler for o in opts], active, True)
+            except Exception:
+                for q, X in req.items():
+                    rec[q]["X"].append(X.copy())
+                    rec[q]["f"].append(np.nan)
+                    rec[q]["g"].append(np.full(X.size, np.nan))
+                raise
+            ans = {}
+            for q, X in req.items():
+                L = -res[q].LL
+                dL = np.concatenate([-np.atleast_1d(res[q].dLL[h.derivname]).reshape(-1) for h in info])
+                rec[q]["X"].append(X.copy())
+                rec[q]["f"].append(L)
+                rec[q]["g"].append(dL)
+                ans[q] = (L, dL)
+            return ans
+
+        mins = minimize_lockstep([X0] * Q, Fbatch, length=n, method=methods[name])
+        o2 = [clip_hyps(set_opt(Xopt, opt, info)) for Xopt, _, _ in mins]
+        final = evaluate(posts, o2, [True] * Q, False)
+        for q, (Xopt, fX, nls) in enumerate(mins):
+            out.append(dict(result=final[q], opt_transhyp=Xopt, opt_L=-fX[-1], fX=fX, line_searches=nls,
+                            evaluations=len(rec[q]["X"]), vbopt=o2[q], hypinfo=info,
+                            X_evals=rec[q]["X"], f_evals=rec[q]["f"], g_evals=rec[q]["g"]))
+    return out

@@ -195,14 +195,24 @@ def run(post: Posterior, engine: EStepEngine, opt: dict, *, total_N: Optional[in
 
 
 def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = None, *,
-               total_N: Optional[int] = None):
+               total_N: Optional[int] = None, opts=None, active=None, calc_deriv: bool = False):
     """R EM trials of one (K, S) cell in one device-side loop (vbhem_em_run_trials):
     per iteration the batched E-step, one kernel with every trial's bound, M-step,
     prelude and stopping rule, and one that keeps what the stopping trials leave;
     the host only waits for a word per iteration.  ``engine`` is a device
     :class:`EStepEngine` with ``trials == len(posts)``.  Returns what
     :func:`vbhem_amd.em.vbhem_h3m_c_trials` returns (an unstable trial's ``syn`` is
-    None).  One rank; no bound derivatives."""
+    None).  One rank.
+
+    With any of ``opts``, ``active`` or ``calc_deriv`` the loop is
+    vbhem_em_run_trials_hyp: ``opts[r]`` are trial r's own options (``opt`` when None;
+    ``max_iter``, ``minDiff``, ``Nv`` and the length of ``W0`` equal in all of them), a
+    slot with ``active[r]`` false is frozen from the start (it must still carry a finite
+    posterior: its clusters ride along in every E-step) and its result is ``None``, and
+    with ``calc_deriv`` every result's ``dLL`` holds the derivatives of its last bound
+    (on the device, csrc/vbhem_em_trials_derivs.hip) as :func:`run` builds them: clipped
+    and transformed with the trial's own options and ``hyp_clipped``, NaN when the trial
+    ends unstable.  ``best`` is taken over the active trials."""
     from . import host
     from .em import TrialsResult, tilde_n
     if not isinstance(engine, EStepEngine):
@@ -210,13 +220,25 @@ def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = 
     R = len(posts)
     if R < 1 or engine.trials != R:
         raise ValueError("engine.trials must equal len(posts)")
+    hyp_entry = opts is not None or active is not None or calc_deriv
     covmode = engine.base.covmode
     total_N = engine.N if total_N is None else int(total_N)
     opt = dict(opt)
     if max_iter is not None:
         opt["max_iter"] = int(max_iter)
+    if opts is None:
+        opts = [opt] * R
+    else:
+        if len(opts) != R:
+            raise ValueError("opts must hold one options dict per trial")
+        opts = [dict(o, max_iter=int(max_iter)) if max_iter is not None else o for o in opts]
+        opt = opts[0]
+    act = np.ones(R, dtype=np.int32) if active is None else np.ascontiguousarray(
+        [1 if x else 0 for x in active], dtype=np.int32)
+    if act.size != R:
+        raise ValueError("active must hold one flag per trial")
     pbs = [_PostBuf(P, covmode) for P in posts]
-    ob = _OptBuf(opt)
+    obs = [_OptBuf(o) for o in opts] if hyp_entry else [_OptBuf(opt)]
     K, S = pbs[0].t.K, pbs[0].t.S
     d = pbs[0].a["m"].shape[2]
     if any((pb.t.K, pb.t.S, pb.a["m"].shape[2]) != (K, S, d) for pb in pbs) or engine.K != R * K:
@@ -224,7 +246,11 @@ def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = 
     post_arr = (_capi.PostT * R)(*[pb.t for pb in pbs])
     tN = tilde_n(engine, opt["Nv"], total_N).contiguous()
     lib = _capi.lib()
-    nb = int(lib.vbhem_em_trials_workspace_bytes(ctypes.byref(engine._bt), K, S, R, engine.T))
+    nW = int(obs[0].W0.size)
+    if hyp_entry:
+        nb = int(lib.vbhem_em_trials_hyp_workspace_bytes(ctypes.byref(engine._bt), K, S, R, engine.T, nW))
+    else:
+        nb = int(lib.vbhem_em_trials_workspace_bytes(ctypes.byref(engine._bt), K, S, R, engine.T))
     if nb == 0:
         raise _capi.VbhemError(
             f"vbhem_em_trials_workspace_bytes: unsupported shape (R={R}, K={K}, S={S}, d={d}, "
@@ -236,13 +262,26 @@ def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = 
     iters, stable = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
     Lf = np.zeros(R)
     stats = np.zeros((R, SL))
-    rc = lib.vbhem_em_run_trials(ctypes.byref(engine._bt), _capi.ptr(tN), R, engine.T,
-                                 ctypes.byref(ob.t), post_arr, _p(LogLs), _p(iters), _p(Lf),
-                                 _p(stable), _p(stats), _capi.ptr(engine.hatZ), _capi.ptr(engine.LL),
-                                 _capi.ptr(ws), ws.numel(), engine._stream())
-    _capi.check(rc, "vbhem_em_run_trials")
+    dLL = np.zeros((R, 5 + nW + d)) if calc_deriv else None
+    if hyp_entry:
+        opt_arr = (_capi.EmOptT * R)(*[ob.t for ob in obs])
+        rc = lib.vbhem_em_run_trials_hyp(ctypes.byref(engine._bt), _capi.ptr(tN), R, engine.T, opt_arr,
+                                         _p(act) if active is not None else None, post_arr, _p(LogLs),
+                                         _p(iters), _p(Lf), _p(stable), _p(stats), _capi.ptr(engine.hatZ),
+                                         _capi.ptr(engine.LL), _p(dLL) if dLL is not None else None,
+                                         _capi.ptr(ws), ws.numel(), engine._stream())
+        _capi.check(rc, "vbhem_em_run_trials_hyp")
+    else:
+        rc = lib.vbhem_em_run_trials(ctypes.byref(engine._bt), _capi.ptr(tN), R, engine.T,
+                                     ctypes.byref(obs[0].t), post_arr, _p(LogLs), _p(iters), _p(Lf),
+                                     _p(stable), _p(stats), _capi.ptr(engine.hatZ), _capi.ptr(engine.LL),
+                                     _capi.ptr(ws), ws.numel(), engine._stream())
+        _capi.check(rc, "vbhem_em_run_trials")
     results = []
     for r in range(R):
+        if not act[r]:
+            results.append(None)
+            continue
         it, ok = int(iters[r]), bool(stable[r])
         cols = slice(r * K, (r + 1) * K)
         st = host.unpack_stats(stats[r], K, S, d, covmode)
@@ -250,12 +289,23 @@ def run_trials(posts, engine: EStepEngine, opt: dict, max_iter: Optional[int] = 
                        LL=float(Lf[r]), iters=it, stable=ok, hatZ=engine.hatZ[:, cols].clone(),
                        L_elbo=engine.LL[:, cols].clone(), Nj=st["Nj"] + 1e-50,
                        syn=host.finish_statistics(st, covmode) if ok else None)
+        if dLL is not None:
+            # as run(): clipped and transformed with the trial's own options
+            # (step_fc.m:356-360), or NaN when the trial ended unstable (:362-368)
+            tr = host.transform_derivs(_raw_dict(dLL[r], nW), opts[r], opts[r].get("hyp_clipped"))
+            res.dLL = tr if ok else {k: np.full_like(np.atleast_1d(v), np.nan)
+                                     for k, v in tr.items() if k != "raw"}
         if ok:
             res.point = host.convert_to_point(res.post, covmode)
             res.label = torch.argmax(res.hatZ, dim=1)
         results.append(res)
-    LLall = np.array([x.LL for x in results])
-    return TrialsResult(results=results, LLall=LLall, best=int(np.argmax(LLall)))
+    LLall = np.array([x.LL if x is not None else np.nan for x in results])
+    best = 0 if np.all(np.isnan(LLall)) else int(np.nanargmax(LLall))
+    # raw: what the C entry wrote, slot by slot (posts: the posteriors of the inactive slots,
+    # which have no result)
+    return TrialsResult(results=results, LLall=LLall, best=best,
+                        raw=dict(posts={r: pbs[r].posterior() for r in range(R) if not act[r]},
+                                 iters=iters, L_final=Lf, stable=stable, LogLs=LogLs, dLL=dLL))
 
 
 def _raw_dict(g: np.ndarray, nW: int) -> dict:

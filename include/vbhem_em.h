@@ -148,6 +148,33 @@ int vbhem_em_run_trials(const vbhem_base_t *base, const double *tildeN_dev, int 
                         double *L_final, int *stable, double *stats_out, double *hatZ_dev,
                         double *LL_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The same loop with every trial under its OWN hyperparameters, a mask, and the bound's
+ * derivatives on the device: one call evaluates R points of the hyperparameter learner
+ * (vbhem_h3m_c.m:96-160 re-optimises every unique trial; every objective evaluation is
+ * an EM run from the trial's posterior plus the derivatives of its last bound).
+ *
+ * opts [R]: trial r's hyperparameters.  max_iter, minDiff, Nv and W0_len must be equal
+ * in all of them (VBHEM_ERR_ARG otherwise; vbhem_last_error says so).  The device reads
+ * per trial a small table (the five scalars, the bound's four constants, m0, W0^-1) the
+ * host fills once per call.
+ * active [R] or NULL (all active): slot r with active[r] == 0 is frozen from the start
+ * and comes back with iters 0, L_final -inf, stable 0, no LogLs, zero statistics, its
+ * posterior bit for bit and dLL all NaN; its hat_Z / L_elbo columns are not written.
+ * Its clusters still ride along in every batched E-step, whose emission GEMM shifts by
+ * the mean of ALL clusters' means, so an inactive slot must carry a FINITE posterior.
+ * dLL [R][VBHEM_DLL_LEN(d, W0_len)] (host) or NULL: the raw derivatives
+ * (vbhemh3m_lb.m:202-345, as vbhem_em_lower_bound_derivs) of each trial's last
+ * accepted bound, taken at the posterior before its last M-step
+ * (vbhem_em_trials_derivs.hip); all NaN for a trial that ends unstable.
+ * Everything else, and the limits, as vbhem_em_run_trials. */
+size_t vbhem_em_trials_hyp_workspace_bytes(const vbhem_base_t *base, int KT, int S, int R, int T,
+                                           int W0_len);
+int vbhem_em_run_trials_hyp(const vbhem_base_t *base, const double *tildeN_dev, int R, int T,
+                            const vbhem_em_opt_t *opts, const int *active, vbhem_post_t *posts,
+                            double *LogLs, int *iters, double *L_final, int *stable,
+                            double *stats_out, double *hatZ_dev, double *LL_dev, double *dLL,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* vbhemh3m_lb.m:202-345: the raw derivatives of the bound with respect to the
  * hyperparameters (posterior held fixed; no clipping, no change of variables --
  * vbhem_amd/hyp.py applies :326-356), from the posterior and its prelude outputs. */
