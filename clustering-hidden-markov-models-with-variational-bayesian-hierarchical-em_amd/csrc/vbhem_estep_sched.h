@@ -35,3 +35,11 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
 const char *last_kernel(int pass);
 
 }  // namespace vbhem
+
+// (exported for the tests, not part of the public interface) where the fused call of R
+// trials carves its gated schedule's buffers in the workspace: out [5] = bases per group,
+// then the byte offsets of the gate lists ([K][group] ints), their totals ([K] ints), the
+// gate masks ([group] 64-bit words; -1: none, K > 64) and the exact fallback's scratch,
+// which comes last; returns the workspace's bytes (0: bad arguments)
+extern "C" size_t vbhem_fused_workspace_layout(const vbhem_base_t *base, const vbhem_cluster_t *clus,
+                                               int T, int R, long long *out);

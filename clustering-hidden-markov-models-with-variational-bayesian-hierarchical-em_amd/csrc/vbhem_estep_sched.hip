@@ -23,8 +23,8 @@ std::atomic<size_t> g_debug_extra_lds{0};
 
 // the kernels the last call of this host thread ran for its recursion passes
 // (vbhem_last_kernel: what a benchmark line names, taken from the launch itself)
-// ([2]: the fused call's gated statistics kernel family)
-thread_local std::string g_last_kernel[3];
+// ([2]: the fused call's gated statistics kernel family, [3]: its finishing kernel)
+thread_local std::string g_last_kernel[4];
 std::string split_name(const SplitArgs &a) {
   return "vbhem::fb_split_kernel<" + std::to_string(a.S) + ", " + std::to_string(a.lpc) + ", " +
          std::to_string(a.mode) + ">";
@@ -84,6 +84,7 @@ struct Ws {
   int slab_len;
   int *fpre, *flags;                // the flag head (kFlagPre), then [0]=count [1]=total [2..] list
   int *gate_cnt, *list, *list_tot;  // gated schedule: [nslab][K], [K][group], [K]
+  unsigned long long *gmask;        // gated schedule, K <= 64: [group] gate masks (else null)
   double *Atg;                      // gated schedule: [K][S][S] A' for the backward pass
   double *scratch, *nu1, *xi, *tnu, *Z, *slabs;
   double *E, *W, *bias, *shift;     // emission GEMM (split path)
@@ -151,6 +152,9 @@ size_t carve_fused(void *ws, const vbhem_base_t *b, const vbhem_cluster_t *c, in
                   ? cv.take<double>((size_t)l4s_max_slots(kExactThreads, K) *
                                     l4s_part_len(S, us_nup(NU)))
                   : nullptr;
+  // the gate masks, a word per base of the group (whatever the switches say: the size
+  // depends on the shape alone)
+  w.gmask = gate_masks_supported(K) ? cv.take<unsigned long long>(gate_mask_words(g)) : nullptr;
   // the exact fallback's scratch last: its size does not move the hot buffers
   w.scratch = cv.take<double>(exact_stride(S, SB, T) * kExactThreads);
   return cv.off + 256;
@@ -480,7 +484,7 @@ int run_fb(const FbCtx &c, const Pass &p, double *Ebuf, long long e_ld, double *
 namespace vbhem {
 
 const char *last_kernel(int pass) {
-  return (pass >= 0 && pass <= 2) ? g_last_kernel[pass].c_str() : "";
+  return (pass >= 0 && pass <= 3) ? g_last_kernel[pass].c_str() : "";
 }
 
 size_t pairs_workspace_bytes(const vbhem_base_t *b, const vbhem_cluster_t *c, int T, bool need_tnu) {
@@ -584,6 +588,9 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
     return set_error(VBHEM_ERR_UNSUPPORTED, "statistics tile does not fit (S or d too large)");
   sa.gate_cnt = gated ? w.gate_cnt : nullptr;
   sa.list = w.list; sa.list_tot = w.list_tot; sa.list_cap = w.group;
+  // K <= 64: the responsibility kernel leaves a gate mask per base, gate_list_kernel
+  // ranks from those instead of reading Z again
+  sa.gmask = gated && !sw.NO_GATE_MASKS ? w.gmask : nullptr;
   // chunks of >= kChunkMinBases bases; the first group has the most, and in the
   // gated schedule its kernels write (not add to) every entry of slabs [0, nslab_used)
   auto chunks = [&w](int nb) { return std::min(w.nslab, (nb + kChunkMinBases - 1) / kChunkMinBases); };
@@ -633,6 +640,13 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
   sa.fold = 0;
   const RespPlan resp = plan_resp(shape, fold, sw);
   const GatedPlan l4reduce = plan_list4_reduce(shape);
+  // one base group whose gate-list pass accumulated the gated sums: the finishing kernel
+  // reduces the partials itself (stats_final_fold_kernel: no list4_stats_reduce_kernel
+  // launch, no pass through slab 0); final_l4w: that pass's waves, final_ev0: the
+  // statistics span left open for it
+  const bool may_fold_final = base->N <= w.group && !sw.NO_FINAL_FOLD;
+  int final_l4w = 0;
+  hipEvent_t final_ev0 = nullptr;
   for (int g0 = 0; g0 < base->N; g0 += w.group) {
     const int g1 = std::min(base->N, g0 + w.group);
     const long long e_ld = (long long)w.group * SB;
@@ -675,6 +689,11 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
       if (l4w > 0) {
         ss = l4reduce.stats_slabs;
         g_last_kernel[2] = "vbhem::list4_stats_reduce_kernel";
+        if (may_fold_final && sa.assign) {
+          final_l4w = l4w;
+          final_ev0 = ev0;
+          break;  // (the only group)
+        }
         e = launch_list4_stats_reduce(sa, l4reduce, w.l4parts, l4w, st);
         if (e != hipSuccess) return hip_fail(e, "list4_stats_reduce_kernel");
       } else {
@@ -691,9 +710,18 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
     }
     timing_stop(kTimeStats, ev0, st);
   }
-  e = launch_stats_final(w.slabs, nslab_used, stats_slabs, w.slab_len, sa.KT, S, sa.SL, stats_dev,
-                         st, w.fpre, done_word, done_val);
-  if (e != hipSuccess) return hip_fail(e, "stats_final_kernel");
+  if (final_l4w > 0) {
+    e = launch_stats_final_fold(sa, l4reduce, w.l4parts, final_l4w, nslab_used, stats_dev, st, w.fpre,
+                                done_word, done_val);
+    if (e != hipSuccess) return hip_fail(e, "stats_final_fold_kernel");
+    g_last_kernel[3] = "vbhem::stats_final_fold_kernel";
+    timing_stop(kTimeStats, final_ev0, st);
+  } else {
+    e = launch_stats_final(w.slabs, nslab_used, stats_slabs, w.slab_len, sa.KT, S, sa.SL, stats_dev,
+                           st, w.fpre, done_word, done_val);
+    if (e != hipSuccess) return hip_fail(e, "stats_final_kernel");
+    g_last_kernel[3] = "vbhem::stats_final_kernel";
+  }
   guard.fpre = nullptr;
   return VBHEM_OK;
 }
@@ -701,3 +729,18 @@ int sched_estep_fused(const vbhem_base_t *base, const vbhem_cluster_t *clus, int
 }  // namespace vbhem
 
 extern "C" size_t vbhem_debug_extra_lds(size_t bytes) { return g_debug_extra_lds.exchange(bytes); }
+
+extern "C" size_t vbhem_fused_workspace_layout(const vbhem_base_t *base, const vbhem_cluster_t *clus,
+                                               int T, int R, long long *out) {
+  if (!base || !clus || !out || R < 1) return 0;
+  Ws w;
+  char *const origin = reinterpret_cast<char *>(256);  // (an address to measure from, never read)
+  const size_t bytes = carve_fused(origin, base, clus, T, w, R);
+  auto at = [&](const void *q) { return q ? (long long)(static_cast<const char *>(q) - origin) : -1ll; };
+  out[0] = w.group;
+  out[1] = at(w.list);
+  out[2] = at(w.list_tot);
+  out[3] = at(w.gmask);
+  out[4] = at(w.scratch);
+  return bytes;
+}

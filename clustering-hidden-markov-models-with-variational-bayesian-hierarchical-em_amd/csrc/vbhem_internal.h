@@ -126,6 +126,10 @@ struct StatsArgs {
   int *list;       // [K][list_cap] bases i with Z(i, j) > 1e-8, ascending i
   int *list_tot;   // [K]
   int list_cap;
+  // the gate masks (K <= 64; null: none): per base of the group one word, bit j set when
+  // pair (i, j) passes the gate -- written by the responsibility kernels from the very
+  // comparison they count into gate_cnt, read by gate_list_kernel instead of Z
+  unsigned long long *gmask;  // [group]
   int PB;          // pairs per batch of stats_list_kernel
   int assign;      // gated schedule, first group: write the slab entries instead of adding
   int KT, SL;      // batched trials: clusters per trial (K = R * KT) and the per-trial
@@ -500,5 +504,11 @@ StatsKernel stats_mfma_kernel(const GatedPlan &gp);  // stats_list_m_kernel's in
 hipError_t launch_stats_final(const double *slabs, int nslab, int nslab_stats, int slab_len, int KT,
                               int S, int SL, double *out, hipStream_t st, int *fpre = nullptr,
                               unsigned long long *done = nullptr, unsigned long long done_val = 0);
+// the two in one launch (stats_final_fold_kernel) for a call of one base group whose
+// gate-list pass accumulated the gated sums: launch_list4_stats_reduce's arguments (a.assign
+// set), then launch_stats_final's; the packed statistics are the two launches' bit for bit
+hipError_t launch_stats_final_fold(const StatsArgs &a, const GatedPlan &gp, const double *parts, int nw,
+                                   int nslab, double *out, hipStream_t st, int *fpre = nullptr,
+                                   unsigned long long *done = nullptr, unsigned long long done_val = 0);
 
 }  // namespace vbhem

@@ -8,6 +8,8 @@
 //   vhem_resp_kernel   the VHEM mode's responsibilities Z, weights w = Z omega_b and
 //                      partial sums Nj, LogL (hem_h3m_c_step.m:293-314, 430, 443); the
 //                      statistics kernels then sum under its gate w > 0 (Gate<kGateVhem>)
+// For K <= 64 each of them also stores the gate mask of every base (StatsArgs::gmask), from
+// the comparison that feeds the per-chunk gate counts; gate_list_kernel ranks from those.
 // Grid: x = chunk of consecutive bases.  All sums run in a fixed order (no atomics on
 // doubles).  Which kernel runs: plan_resp (vbhem_stats_plan.h).
 #include <hip/hip_runtime.h>
@@ -35,6 +37,13 @@ namespace vbhem {
 #define VBHEM_RESP_WPE 4
 #endif
 typedef unsigned int resp_u2 __attribute__((ext_vector_type(2)));
+
+// The gate mask of a base (StatsArgs::gmask, K <= 64) from the ballot of the gate test over
+// a wavefront whose lane groups of G lanes hold a base each, a cluster per lane: the G bits
+// of group sub, bit j = cluster j.
+__device__ __forceinline__ unsigned long long group_bits(unsigned long long ballot, int sub, int G) {
+  return G >= 64 ? ballot : (ballot >> (sub * G)) & ((1ull << G) - 1ull);
+}
 
 // KP: K when it is a power of two <= 64 (every lane of a base group holds a cluster:
 // the group reductions unroll and the stores need no lane mask), else 0
@@ -95,6 +104,10 @@ __global__ __launch_bounds__(kRespThreads) __attribute__((amdgpu_waves_per_eu(VB
         p.hatZ + (size_t)b0 * KP, (short)0, nb * KP * 8, 0x00020000);
     const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
         p.Z + (size_t)(b0 - p.i_buf0) * KP, (short)0, nb * KP * 8, 0x00020000);
+    // the gate masks: a word per base from lane 0 of its group (no masks: no records,
+    // every store dropped)
+    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
+        p.gmask ? p.gmask + (b0 - p.i_buf0) : nullptr, (short)0, p.gmask ? nb * 8 : 0, 0x00020000);
     auto step = [&](int ib, double tnb, double llb) {
 #pragma clang fp contract(off)
       const bool iv = ib < b1;
@@ -113,7 +126,11 @@ __global__ __launch_bounds__(kRespThreads) __attribute__((amdgpu_waves_per_eu(VB
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(resp_u2, Z), rz, off, 0, 0);
       // (no branch in the step: the lanes past the chunk add zeros)
       accNj[(wave * BP + sub) * KP + gl] += iv ? Z : 0.0;
-      atomicAdd(&gcnt[gl], (iv && Z > kGateZ) ? 1 : 0);
+      const bool gt = iv && Z > kGateZ;
+      atomicAdd(&gcnt[gl], gt ? 1 : 0);
+      const unsigned long long gm = group_bits(__ballot(gt), sub, KP);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(resp_u2, gm), rm,
+                                            (iv && gl == 0) ? (ib - b0) * 8 : 0x7ffffff0, 0, 0);
       l1 += iv ? Z * llb : 0.0;
       l7 += iv ? hz * log(hz) : 0.0;
     };
@@ -123,6 +140,8 @@ __global__ __launch_bounds__(kRespThreads) __attribute__((amdgpu_waves_per_eu(VB
       llb = p.LL[(size_t)ii * KP + gl];
     };
     int i = b0 + wave * BP + sub;
+    // (all of a wave's steps loaded up front -- seven at C4 -- measured slower than these
+    // two buffers: DESIGN.md 8)
     double tA, lA, tB, lB;
     ld(i, tA, lA);
     for (; i - sub < b1; i += 2 * stride) {
@@ -150,15 +169,21 @@ __global__ __launch_bounds__(kRespThreads) __attribute__((amdgpu_waves_per_eu(VB
       double sm = gl < K ? exp(lz - mx) : 0.0;
       sm = group_sum(sm, G);
       const double lse = mx + log(sm);
+      bool gt = false;
       if (iv && gl < K) {
         const double hz = exp(lz - lse) + 1e-50;
         const double Z = hz * tnb;
         p.hatZ[(size_t)ib * K + gl] = hz;
         p.Z[(size_t)(ib - p.i_buf0) * K + gl] = Z;
         accNj[(wave * BPW + sub) * K + gl] += Z;
-        if (Z > kGateZ) atomicAdd(&gcnt[gl], 1);
+        gt = Z > kGateZ;
+        if (gt) atomicAdd(&gcnt[gl], 1);
         l1 += Z * llb;
         l7 += hz * log(hz);
+      }
+      if (p.gmask) {  // (uniform; the step runs on every lane of the wave)
+        const unsigned long long gm = group_bits(__ballot(gt), sub, G);
+        if (iv && gl == 0) p.gmask[ib - p.i_buf0] = gm;
       }
     };
 #if VBHEM_RESP_UNROLL == 2
@@ -301,6 +326,7 @@ __global__ __launch_bounds__(kRespThreads) void resp_trials_kernel(const StatsAr
 #pragma unroll
       for (int s = 0; s < kRespSlots; ++s) lse[s] = tr[s] == r ? l : lse[s];
     }
+    bool gt0 = false;  // slot 0's gate test (K <= 64: the only slot with clusters)
     if (iv) {
 #pragma unroll
       for (int s = 0; s < kRespSlots; ++s) {
@@ -311,10 +337,16 @@ __global__ __launch_bounds__(kRespThreads) void resp_trials_kernel(const StatsAr
         p.hatZ[(size_t)i * K + j] = hz;
         p.Z[(size_t)(i - p.i_buf0) * K + j] = Z;
         accNj[(wave * BPW + sub) * K + j] += Z;
-        if (Z > kGateZ) atomicAdd(&gcnt[j], 1);
+        const bool gt = Z > kGateZ;
+        if (gt) atomicAdd(&gcnt[j], 1);
+        if (s == 0) gt0 = gt;
         l1[s] += Z * LL[j];
         l7[s] += hz * log(hz);
       }
+    }
+    if (p.gmask) {  // (uniform, K <= 64; the loop's trip count is the wave's)
+      const unsigned long long gm = group_bits(__ballot(gt0), sub, G);
+      if (iv && gl == 0) p.gmask[i - p.i_buf0] = gm;
     }
   }
   for (int r = 0; r < R; ++r) {
@@ -408,6 +440,7 @@ __global__ __launch_bounds__(kRespThreads) void vhem_resp_kernel(const StatsArgs
 #pragma clang fp contract(off)
     const double ni = p.tildeN[i], ob = p.omegaB[i];
     const double *LL = p.LL + (size_t)i * K;
+    unsigned long long gm = 0ull;  // this lane's clusters of base i that pass the gate
     for (int r0 = 0; r0 < R; r0 += TPS) {  // wave-uniform
       const int r = r0 + sub;
       const bool rv = r < R;
@@ -429,10 +462,17 @@ __global__ __launch_bounds__(kRespThreads) void vhem_resp_kernel(const StatsArgs
           p.hatZ[(size_t)i * K + jb + j] = Z;
           p.Z[(size_t)(i - p.i_buf0) * K + jb + j] = w;
           accNj[wave * K + jb + j] += Z;
-          if (w > Gate<kGateVhem>::value) atomicAdd(&gcnt[jb + j], 1);
+          const bool gt = w > Gate<kGateVhem>::value;
+          if (gt) atomicAdd(&gcnt[jb + j], 1);
+          if (gt && p.gmask) gm |= 1ull << (jb + j);  // (masks: K <= 64)
         }
         if (gl == 0) accL[wave * R + r] += lse;
       }
+    }
+    if (p.gmask) {  // (uniform) the lanes' bits into the base's word
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) gm |= __shfl_xor(gm, off, 64);
+      if (lane == 0) p.gmask[i - p.i_buf0] = gm;
     }
   }
   __syncthreads();

@@ -12,6 +12,8 @@
 //                      and the bases at once: a (K*S) x (N*Sb) x NU GEMM on
 //                      v_mfma_f64_16x16x4f64, K-dim streamed in batches of NBB bases.
 //   stats_final_kernel fixed-order sum of the per-chunk slabs.
+//   stats_final_fold_kernel  the same finish with list4_stats_reduce_kernel's reduction
+//                      inside it (one base group, sums accumulated in fb_list4_kernel).
 //
 // Grid: x = chunk of consecutive bases, y = group of JG clusters (rows j*S+s),
 // so no tile is loaded twice; every block keeps its whole (JG*S) x NU output
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_kernel(const StatsArgs p) {
 // p, p+16, p+32, ... (128-B rows, four loads in flight per thread), then the 16
 // partials are added in fixed order -- deterministic; ~slab_len/16 blocks (C4:
 // 506) keep every CU's loads in flight (32-column blocks left it latency-bound).
-constexpr int kFinalCols = 16, kFinalParts = 16;
+// (The pieces shared with stats_final_fold_kernel: vbhem_stats_dev.h.)
 __global__ __launch_bounds__(256) void stats_final_kernel(const double *slabs, int nslab_all,
                                                           int nslab_stats, int slab_len, int KT,
                                                           int S, int SL, double *out, int *fpre,
@@ -272,68 +274,73 @@ __global__ __launch_bounds__(256) void stats_final_kernel(const double *slabs, i
                                                           unsigned long long *done,
                                                           unsigned long long done_val) {
   __shared__ double part[kFinalParts][kFinalCols];
-  // the call's last kernel closes the flag head (kFlagPre): the total kept, the counters
-  // zeroed, the tag written -- the next call's in-kernel preparation finds them clean.
-  // With a completion word, counter [2] (fb_exact_kernel's blocks-done, zero between
-  // passes) counts this kernel's finished blocks instead: the last one resets it
-  if (fpre && blockIdx.x == 0 && threadIdx.x == 0) {
-    int *fc = fpre + kFlagPre;
-    fpre[2] = fc[1];
-    for (int c = 0; c < kFlagHead; ++c)
-      if (!(done && c == 2)) fc[c] = 0;
-    *reinterpret_cast<unsigned long long *>(fpre) = tag;
-  }
+  if (fpre && blockIdx.x == 0 && threadIdx.x == 0) final_close_head(fpre, tag, done != nullptr);
   const int c = threadIdx.x % kFinalCols, pp = threadIdx.x / kFinalCols;
   const int x = blockIdx.x * kFinalCols + c;
   // resp_kernel's columns (Nj, Lt1, Lt7) have a partial in every chunk's slab; the
   // gated statistics' only in their kernel's parts
   const int xs = x % SL, lt = KT * (1 + S + S * S);
   const int nslab = (xs < KT || (xs >= lt && xs < lt + 2)) ? nslab_all : nslab_stats;
-  double acc = 0.0;
-  if (x < slab_len) {
-    int k = pp;
-    for (; k + 3 * kFinalParts < nslab; k += 4 * kFinalParts) {
-      const double *q = slabs + (size_t)k * slab_len + x;
-      const double v0 = q[0], v1 = q[(size_t)kFinalParts * slab_len],
-                   v2 = q[(size_t)2 * kFinalParts * slab_len], v3 = q[(size_t)3 * kFinalParts * slab_len];
-      acc += v0;
-      acc += v1;
-      acc += v2;
-      acc += v3;
-    }
-    for (; k < nslab; k += kFinalParts) acc += slabs[(size_t)k * slab_len + x];
-  }
-  part[pp][c] = acc;
+  part[pp][c] = x < slab_len ? final_partial(slabs, nslab, slab_len, x, pp) : 0.0;
   __syncthreads();
   if (pp == 0 && x < slab_len) {
     double s = part[0][c];
 #pragma unroll
     for (int q = 1; q < kFinalParts; ++q) s += part[q][c];
-    // a lost flag-head handshake (kFlagLost, fb_bwd2_kernel): results untrusted
-    if (fpre && __hip_atomic_load(fpre + kFlagLost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                    kFlagLostMark)
-      s = __builtin_nan("");
-    if (done)  // written through to the system (the host polls the word, not an event)
-      __hip_atomic_store(reinterpret_cast<unsigned long long *>(out + x), __double_as_longlong(s),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    else
-      out[x] = s;
+    final_store(out + x, s, fpre, done != nullptr);
   }
-  if (done && fpre) {
-    // every store of this block acknowledged (written through at system scope: what a
-    // system-scope release would wait for, without its L2 write-back), then one count
-    // per block; the last block to count publishes the word after all of them
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  if (done && fpre) final_publish(fpre, done, done_val);
+}
+
+// stats_final_fold_kernel: the finish of a call whose gate-list pass accumulated the gated
+// sums (fb_list4_kernel's partials, vbhem_list4_slots.h) over one base group -- what
+// list4_stats_reduce_kernel followed by stats_final_kernel compute, in one launch and
+// without the round trip through slab 0.  Blocks [0, K S): block (j, s) sums state s's row
+// of cluster j over the cluster's slots (list4_reduce_row, the reduction's own order),
+// shifts it back by z (su_entry) and stores it in the packed statistics; the value passes
+// through the `0.0 +` that stats_final_kernel's sum over the one slab applied, so the bits
+// are those of the two launches.  The blocks after them sum the responsibility kernels'
+// columns (Nj, Lt1, Lt7 of each trial section) over every chunk's slab as
+// stats_final_kernel does, 16 columns per block on the first 256 threads.  Block 0 closes
+// the flag head; the completion word counts every block.
+__global__ __launch_bounds__(kL4rThreads) void stats_final_fold_kernel(
+    const StatsArgs p, const double *parts, int nw, int nslab_all, double *out, int *fpre,
+    unsigned long long tag, unsigned long long *done, unsigned long long done_val) {
+  extern __shared__ double lds[];
+  __shared__ int plan[2];
+  __shared__ double part[kL4rParts][kL4rCols];
+  const int tid = threadIdx.x, K = p.K, S = p.S, KT = p.KT;
+  if (fpre && blockIdx.x == 0 && tid == 0) final_close_head(fpre, tag, done != nullptr);
+  if ((int)blockIdx.x < K * S) {
+    const int j = blockIdx.x / S, s2 = blockIdx.x - j * S;
+    const int NO = S * p.NU + S + S * S, tr = j / KT, jt = j - tr * KT;
+    double *red = lds;  // [S][NU] | [S] | [S][S]: row s2 filled; then z [d]
+    list4_reduce_row(p, parts, nw, j, s2, tid, red, plan, part);
+    for (int o = tid; o < NO; o += kL4rThreads) {
+      if (su_row(p, o) != s2) continue;
+      size_t at;
+      double s = 0.0;  // (stats_final_kernel's sum over slab 0 alone: -0.0 becomes 0.0)
+      s += su_entry(p, red, red + NO, o, jt, at);
+      final_store(out + (size_t)tr * p.SL + at, s, fpre, done != nullptr);
+    }
+  } else {
+    // column r of the trials' (Nj [KT] | Lt1, Lt7) entries
+    double(*fp)[kFinalCols] = reinterpret_cast<double(*)[kFinalCols]>(&part[0][0]);
+    const int c = tid % kFinalCols, pp = tid / kFinalCols;
+    const int r = ((int)blockIdx.x - K * S) * kFinalCols + c, ncol = (K / KT) * (KT + 2);
+    const int tr = r / (KT + 2), q = r - tr * (KT + 2);
+    const int x = tr * p.SL + (q < KT ? q : KT * (1 + S + S * S) + (q - KT));
+    const bool act = pp < kFinalParts && r < ncol;
+    if (pp < kFinalParts) fp[pp][c] = act ? final_partial(p.slabs, nslab_all, p.slab_len, x, pp) : 0.0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      int *cnt = fpre + kFlagPre + 2;
-      const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev == (int)gridDim.x - 1) {
-        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(done, done_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+    if (pp == 0 && act) {
+      double s = fp[0][c];
+#pragma unroll
+      for (int k = 1; k < kFinalParts; ++k) s += fp[k][c];
+      final_store(out + x, s, fpre, done != nullptr);
     }
   }
+  if (done && fpre) final_publish(fpre, done, done_val);
 }
 
 // ---------------------------------------------------------------------------
@@ -364,6 +371,20 @@ hipError_t launch_stats_final(const double *slabs, int nslab, int nslab_stats, i
   if (nslab_stats < 1 || nslab_stats > nslab || SL < 1 || slab_len % SL != 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(stats_final_kernel, dim3((slab_len + kFinalCols - 1) / kFinalCols), dim3(256),
                      0, st, slabs, nslab, nslab_stats, slab_len, KT, S, SL, out, fpre,
+                     fpre ? flag_tag() : 0ull, fpre ? done : nullptr, done_val);
+  return hipGetLastError();
+}
+
+hipError_t launch_stats_final_fold(const StatsArgs &a, const GatedPlan &gp, const double *parts, int nw,
+                                   int nslab, double *out, hipStream_t st, int *fpre,
+                                   unsigned long long *done, unsigned long long done_val) {
+  if (!gp.ok || gp.kernel != GatedStats::kList4Reduce || gp.cap != a.S || !parts || nw < 1 || !a.uz ||
+      !a.list_tot || !a.assign || nslab < 1 || a.KT < 1 || a.K % a.KT != 0 ||
+      a.slab_len != (a.K / a.KT) * a.SL)
+    return hipErrorInvalidValue;
+  const int ncol = (a.K / a.KT) * (a.KT + 2);
+  hipLaunchKernelGGL(stats_final_fold_kernel, dim3(a.K * a.S + (ncol + kFinalCols - 1) / kFinalCols),
+                     dim3(kL4rThreads), gp.lds, st, a, parts, nw, nslab, out, fpre,
                      fpre ? flag_tag() : 0ull, fpre ? done : nullptr, done_val);
   return hipGetLastError();
 }

@@ -25,9 +25,11 @@ namespace vbhem {
 // cluster j's list is the gate count of the chunks before it; inside the chunk
 // the bases are ranked by wave ballots (masks in LDS, one barrier per slice).
 // Deterministic (no global atomics): the same list every call.
+// MASK (K <= 64): the gate test read from the responsibility kernel's masks
+// (StatsArgs::gmask, 8 bytes per base) instead of made again on the K doubles of Z.
 // ---------------------------------------------------------------------------
 
-template <int GM>
+template <int GM, bool MASK>
 __global__ __launch_bounds__(kListThreads) void gate_list_kernel(const StatsArgs p) {
   extern __shared__ int ish[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -89,15 +91,25 @@ __global__ __launch_bounds__(kListThreads) void gate_list_kernel(const StatsArgs
   for (int i0 = b0; i0 < b1; i0 += kListThreads) {
     const int i = i0 + tid;
     const bool iv = i < b1;
-    const double *Zi = p.Z + (size_t)((iv ? i : b0) - p.i_buf0) * K;
-    for (int j0 = 0; j0 < K; j0 += kJB) {
-      double z[kJB];
+    if constexpr (MASK) {
+      // K <= 64: the base's gate mask (one coalesced load per slice), the test the
+      // responsibility kernel made when it counted gate_cnt
+      const unsigned long long gm = iv ? p.gmask[i - p.i_buf0] : 0ull;
+      for (int j = 0; j < K; ++j) {
+        const unsigned long long m = __ballot((gm >> j) & 1ull);
+        if (lane == 0) msk[wave * K + j] = m;
+      }
+    } else {
+      const double *Zi = p.Z + (size_t)((iv ? i : b0) - p.i_buf0) * K;
+      for (int j0 = 0; j0 < K; j0 += kJB) {
+        double z[kJB];
 #pragma unroll
-      for (int q = 0; q < kJB; ++q) z[q] = j0 + q < K ? Zi[j0 + q] : 0.0;
+        for (int q = 0; q < kJB; ++q) z[q] = j0 + q < K ? Zi[j0 + q] : 0.0;
 #pragma unroll
-      for (int q = 0; q < kJB; ++q) {
-        const unsigned long long m = __ballot(iv && z[q] > Gate<GM>::value);
-        if (lane == 0 && j0 + q < K) msk[wave * K + j0 + q] = m;
+        for (int q = 0; q < kJB; ++q) {
+          const unsigned long long m = __ballot(iv && z[q] > Gate<GM>::value);
+          if (lane == 0 && j0 + q < K) msk[wave * K + j0 + q] = m;
+        }
       }
     }
     __syncthreads();
@@ -532,7 +544,11 @@ __global__ __launch_bounds__(64 * kSuWaves) void stats_list_g_kernel(const Stats
 hipError_t launch_gate_list(const StatsArgs &a, int nchunk, hipStream_t st) {
   // (above 64 KB the launch needs the attribute)
   const size_t lds = gate_list_lds(a.K);
-  auto *fn = a.vhem ? &gate_list_kernel<kGateVhem> : &gate_list_kernel<kGateVbhem>;
+  if (a.gmask && a.K > 64) return hipErrorInvalidValue;
+  // (with masks the gate is in them: one instantiation serves both modes)
+  auto *fn = a.gmask ? &gate_list_kernel<kGateVbhem, true>
+             : a.vhem ? &gate_list_kernel<kGateVhem, false>
+                      : &gate_list_kernel<kGateVbhem, false>;
   hipError_t e = set_dyn_lds(reinterpret_cast<const void *>(fn), lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(nchunk), dim3(kListThreads), lds, st, a);

@@ -209,65 +209,20 @@ __global__ __launch_bounds__(64 * kSmWaves) void stats_list_m_kernel(const Stats
 }
 
 // list4_stats_reduce_kernel: the gated sums that fb_list4_kernel's accumulating variant
-// left as partials (vbhem_list4_slots.h; U [S][NUP] | N1 [S] | M [S][S] per slot).  Block
-// (j, s) sums state s's row of cluster j -- its NU moments, its N1 entry and its M row,
-// at most 64 columns -- over the cluster's slots: 16 thread groups take a sixteenth of
-// the slots each, in slot order, eight loads in flight, and the sixteen sums are added
-// in group order (fixed: bit-reproducible).  su_output then shifts the row back by z
-// (which needs only the row's own sums) and writes or adds slab 0's sections; a cluster
-// with an empty list gets zeros.
+// left as partials (vbhem_list4_slots.h).  Block (j, s) sums state s's row of cluster j over
+// the cluster's slots (list4_reduce_row, vbhem_stats_dev.h); su_output then shifts the row
+// back by z (which needs only the row's own sums) and writes or adds slab 0's sections.
+// With one base group the finishing kernel does this itself (stats_final_fold_kernel,
+// vbhem_stats_dense.hip) and this kernel is not launched.
 __global__ __launch_bounds__(kL4rThreads) void list4_stats_reduce_kernel(const StatsArgs p,
                                                                         const double *parts, int nw) {
   extern __shared__ double lds[];
   __shared__ int plan[2];
   __shared__ double part[kL4rParts][kL4rCols];
   const int tid = threadIdx.x, S = p.S, j = blockIdx.x / S, s2 = blockIdx.x - j * S;
-  const int NU = p.NU, NUP = us_nup(NU), d = p.d;
-  if (tid == 0) {
-    int nitem = 0, pre = 0;
-    for (int x = 0; x < p.K; ++x) {
-      if (x == j) pre = nitem;
-      nitem += l4s_items(p.list_tot[x]);
-    }
-    const int per = l4s_per_wave(nitem, nw), n = l4s_items(p.list_tot[j]);
-    plan[0] = l4s_slot(pre, j, per);
-    plan[1] = n ? l4s_slot(pre + n - 1, j, per) - plan[0] + 1 : 0;
-  }
-  __syncthreads();
-  const int s0 = plan[0], ns = plan[1];
-  const int NO = S * NU + S + S * S, PL = l4s_part_len(S, NUP);
-  double *red = lds;                                  // [S][NU] | [S] | [S][S]: row s2 filled
-  double *zs = red + NO;                              // [d]
-  for (int a = tid; a < d; a += kL4rThreads) zs[a] = p.uz[a];
-  // column col of the row: a moment, the N1 entry, an M entry -- in a partial, in red
-  const int q = tid / kL4rCols, col = tid - q * kL4rCols;
-  const bool cv = col < NU + 1 + S;
-  const int src = col < NU ? s2 * NUP + col : col == NU ? S * NUP + s2 : S * NUP + S + s2 * S + (col - NU - 1);
-  const int dst = col < NU ? s2 * NU + col : col == NU ? S * NU + s2 : S * NU + S + s2 * S + (col - NU - 1);
-  const int k0 = (int)((long long)ns * q / kL4rParts), k1 = (int)((long long)ns * (q + 1) / kL4rParts);
-  double acc = 0.0;
-  if (cv) {
-    const double *g = parts + (size_t)s0 * PL + src;
-    int k = k0;
-    for (; k + 7 < k1; k += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = g[(size_t)(k + u) * PL];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc += v[u];
-    }
-    for (; k < k1; ++k) acc += g[(size_t)k * PL];
-  }
-  part[q][col] = acc;
-  __syncthreads();
-  if (q == 0 && cv) {
-    double t = part[0][col];
-#pragma unroll
-    for (int x = 1; x < kL4rParts; ++x) t += part[x][col];
-    red[dst] = t;
-  }
-  __syncthreads();
-  if (tid < 64 * kSuWaves) su_output(p, red, zs, 0, 1, j, tid, s2);
+  double *red = lds;  // [S][NU] | [S] | [S][S]: row s2 filled; then z [d]
+  list4_reduce_row(p, parts, nw, j, s2, tid, red, plan, part);
+  if (tid < 64 * kSuWaves) su_output(p, red, red + S * p.NU + S + S * S, 0, 1, j, tid, s2);
 }
 
 // ---------------------------------------------------------------------------

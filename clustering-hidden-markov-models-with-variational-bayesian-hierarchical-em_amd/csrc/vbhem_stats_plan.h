@@ -80,6 +80,11 @@ inline size_t gate_list_lds(int K) {
          (size_t)(kListThreads / 64) * K * sizeof(unsigned long long);
 }
 
+// the gate masks (StatsArgs::gmask): one 64-bit word per base of a group, bit j = pair
+// (i, j) passes the gate -- while a word holds every cluster
+inline bool gate_masks_supported(int K) { return K >= 1 && K <= 64; }
+inline size_t gate_mask_words(size_t group_bases) { return group_bases; }
+
 enum class RespKernel { kVhem, kTrials, kKP, kGeneric };
 struct RespPlan {
   bool ok = false;  // false: K / KT outside the kernel's range

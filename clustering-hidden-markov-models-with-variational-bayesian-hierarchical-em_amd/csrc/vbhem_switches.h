@@ -28,6 +28,8 @@
   X(EM_SPLIT, -1, "the one-chunk emission GEMM in whole (0) or half (1) tiles")                \
   X(EM_NODB, 0, "the chunked emission GEMM on emission_u_kernel, not emission_db_kernel")      \
   X(RESP_GENERIC, 0, "resp_kernel's generic path for every K")                                 \
+  X(NO_GATE_MASKS, 0, "K <= 64: gate_list_kernel re-reads Z, not the responsibility kernel's gate masks") \
+  X(NO_FINAL_FOLD, 0, "list4_stats_reduce_kernel launched, not folded into the finishing kernel") \
   X(SU_BLOCKS, -1, "gated statistics: the block count")                                        \
   X(NO_STATS_G, 0, "gated statistics: no lane-grouped kernel")                                 \
   X(NO_STATS_U, 0, "gated statistics: the covariance-gather kernel")                           \

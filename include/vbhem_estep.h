@@ -346,7 +346,9 @@ const char *vbhem_version(void);
  * schedule, K2-K4 in the dense one), pass 1 the gated schedule's gate-list pass;
  * 2: what summed the gated statistics of the last fused call's last base group,
  * "vbhem::list4_stats_reduce_kernel" (the sums were accumulated in the gate-list
- * pass) or "vbhem::stats_list_kernels";
+ * pass; the name also when the finishing kernel reduced them itself) or
+ * "vbhem::stats_list_kernels"; 3: the last fused call's finishing kernel,
+ * "vbhem::stats_final_kernel" or "vbhem::stats_final_fold_kernel";
  * "" before any such launch. Benchmark labelling only (no reference
  * counterpart). */
 const char *vbhem_last_kernel(int pass);
