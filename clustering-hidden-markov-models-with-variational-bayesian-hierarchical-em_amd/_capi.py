@@ -47,6 +47,18 @@ class EmOptT(ctypes.Structure):  # include/vbhem_em.h vbhem_em_opt_t
                 ("Nv", ctypes.c_double), ("max_iter", _c_int), ("minDiff", ctypes.c_double)]
 
 
+class VhemMixTrialsT(ctypes.Structure):  # include/vhem_em.h vhem_mix_trials_t
+    _fields_ = [("K", _c_int), ("S", _c_int), ("d", _c_int), ("covmode", _c_int),
+                ("omega", _vp), ("prior", _vp), ("A", _vp), ("centres", _vp), ("covars", _vp),
+                ("emit_vcounts", _vp)]
+
+
+class VhemEmOptT(ctypes.Structure):  # include/vhem_em.h vhem_em_opt_t
+    _fields_ = [("inf_norm", ctypes.c_double), ("smooth", ctypes.c_double),
+                ("reg_cov", ctypes.c_double), ("termvalue", ctypes.c_double),
+                ("tau", _c_int), ("max_iter", _c_int), ("min_iter", _c_int)]
+
+
 class SeqsT(ctypes.Structure):  # include/vbhmm_fb.h vbhmm_seqs_t
     _fields_ = [("N", _c_int), ("dim", _c_int), ("maxT", _c_int), ("offsets", _vp), ("x", _vp)]
 
@@ -192,6 +204,11 @@ EXPORTS = {
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "vbhem_em_lower_bound_derivs": (_c_int, [ctypes.POINTER(PostT), ctypes.POINTER(EmOptT), _vp,
                                              _vp, _vp, _vp, _vp]),
+    "vhem_em_trials_workspace_bytes": (_c_size, [ctypes.POINTER(BaseT), _c_int, _c_int, _c_int,
+                                                 _c_int]),
+    "vhem_em_run_trials": (_c_int, [ctypes.POINTER(BaseT), _vp, _vp, _c_int, _c_int,
+                                    ctypes.POINTER(VhemEmOptT), ctypes.POINTER(VhemMixTrialsT),
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "vbhem_hmms_to_h3m": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int] + [_vp] * 15),
     "vbhem_rccl_available": (_c_int, []),
     "vbhem_rccl_unique_id": (_c_int, [_vp]),

@@ -25,6 +25,7 @@
 #include "vbhem_em.h"
 #include "vbhem_em_deriv_terms.h"
 #include "vbhem_em_dev.h"
+#include "vbhem_em_host.h"
 #include "vbhem_em_trial_ctrl.h"
 #include "vbhem_internal.h"
 #include "vbhem_special.h"
@@ -688,10 +689,7 @@ int em_run_host(const vbhem_base_t *base, const double *tildeN_dev, int T, const
 
 // Mapped host memory of the trials loop (its words and the bounds of every trial):
 // a per-device pool like g_mapped_free, of blocks that only grow.
-struct MappedBuf {
-  char *h = nullptr, *d = nullptr;
-  size_t bytes = 0;
-};
+using MappedBuf = vbhem::EmMappedBuf;  // vbhem_em_host.h
 std::map<int, std::vector<MappedBuf>> g_mapped_bufs;
 
 hipError_t acquire_mapped_buf(size_t bytes, MappedBuf &m) {
@@ -751,6 +749,15 @@ const char *trials_unsupported(const vbhem_base_t *base, int K, int S, int R) {
 }
 
 }  // namespace
+
+// what the VHEM trials loop (vhem_em.hip) shares with the one below (vbhem_em_host.h)
+extern "C++" {
+namespace vbhem {
+hipError_t em_wait_flag(const int *flag, int seq, hipStream_t st) { return wait_flag(flag, seq, st); }
+hipError_t em_acquire_mapped_buf(size_t bytes, EmMappedBuf &m) { return acquire_mapped_buf(bytes, m); }
+void em_release_mapped_buf(const EmMappedBuf &m) { release_mapped_buf(m); }
+}  // namespace vbhem
+}  // extern "C++"
 
 int vbhem_em_run_ext(const vbhem_base_t *base, const double *tildeN_dev, int T,
                      const vbhem_em_opt_t *opt, vbhem_post_t *post, double *LogLs, int *iters,

@@ -4,7 +4,9 @@ The classic emhmm clustering call: point-estimate HMMs are clustered into K grou
 HMMs of S states by the variational hierarchical EM of Coviello et al.  One EM
 iteration is one launch of the fused VHEM E-step (``EStepEngine.fused_vhem``:
 recursions, responsibilities, weights and the gated statistic sums on the device);
-everything here is the O(K S d^2) host math around it:
+everything here is the O(K S d^2) host math around it (with hemopt['em_engine'] =
+'device' the EM loop of a chunk of trials runs on the GPU instead, vhem_em_run_trials,
+and only the trials that need a degenerate fix come back to this host loop):
 
 * :func:`hmms_to_h3m` / :func:`h3m_to_hmms` -- hmms_to_h3m.m, h3m_to_hmms.m
 * :func:`hem_mstep` -- hem_mstep_component.m:123-166 from the packed statistics
@@ -44,7 +46,8 @@ def default_hemopt(K: int, S: int, **over) -> dict:
     opt = dict(K=int(K), N=int(S), verbose=0, remove_empty=1, trials=100, reg_cov=0.001,
                termmode="L", termvalue=1e-5, max_iter=100, min_iter=1, sortclusters="f",
                initmode="auto", tau=10, seed=None, Nv=100, inf_norm="nt", smooth=1.0,
-               keep_suboptimal_hmms=0, computeStats=0, covar_type="full", M=1)
+               keep_suboptimal_hmms=0, computeStats=0, covar_type="full", M=1,
+               em_engine="host")
     initopt = dict(iter=30, trials=4, mode="")
     initopt.update(over.pop("initopt", {}) or {})
     unknown = set(over) - set(opt)
@@ -66,6 +69,8 @@ def default_hemopt(K: int, S: int, **over) -> dict:
         raise ValueError("covar_type must be 'full' or 'diag'")
     if opt["initmode"] != "auto" and opt["initmode"] not in INITMODES:
         raise ValueError(f"initmode {opt['initmode']!r}: 'auto' or one of {INITMODES}")
+    if opt["em_engine"] not in ("host", "device"):
+        raise ValueError(f"em_engine {opt['em_engine']!r}: 'host' or 'device'")
     inf_norm_value(opt["inf_norm"], 1, 1, 1)
     return opt
 
@@ -206,15 +211,120 @@ def _stack(hs: List[dict], covmode: int) -> dict:
     return host.vhem_cluster_constants(red, covmode)
 
 
-def hem_h3m_c_trials(h3ms: List[dict], engine, opt: dict, rngs=None) -> List[dict]:
+def device_em_supported(base: BaseSet, K: int, S: int, R: int, opt: dict) -> bool:
+    """Whether a chunk of R trials of K clusters lies inside the shapes of the device EM
+    engine (vhem_em_run_trials): those of the batched E-step with d <= 16, and a
+    ``min_iter`` that lets every trial end within max_iter + 2 E-steps."""
+    max_iter, min_iter = int(opt["max_iter"]), int(opt.get("min_iter", 0))
+    return (1 <= S <= 16 and base.SB <= S and 1 <= base.d <= 16 and R >= 1 and R * K <= 256
+            and max_iter >= 0 and 0 <= min_iter <= max_iter + 1)
+
+
+def _hem_h3m_c_trials_device(h3ms: List[dict], engine, opt: dict, rngs) -> List[dict]:
+    """hem_h3m_c_trials with the loop on the device (vhem_em_run_trials); the trials it
+    flags are rerun by the host engine."""
+    import ctypes
+
+    from . import _capi
+    from .estep import EStepEngine
+    if not isinstance(engine, EStepEngine):
+        raise ValueError("em_engine='device' needs a device EStepEngine")
+    R = len(h3ms)
+    base = engine.base
+    covmode, Kb, d = base.covmode, base.N, base.d
+    K, S = h3ms[0]["prior"].shape
+    if engine.K != R * K:
+        raise ValueError("the trials must share one shape, K = engine.K / trials")
+    T, Nv = int(opt["tau"]), opt["Nv"]
+    reg = float(opt.get("reg_cov", 0.0))
+    inf_norm = inf_norm_value(opt["inf_norm"], T, Nv, Kb)
+    max_iter = int(opt["max_iter"])
+    omegaB = base.omega.to(torch.float64).contiguous()
+    Ni = ((float(Nv) * omegaB) * float(Kb)).contiguous()              # :61
+    add = reg * np.eye(d) if covmode == COV_FULL else reg             # :98-108
+    arr = {k: np.ascontiguousarray(np.stack([np.asarray(h[k], dtype=np.float64) for h in h3ms]))
+           for k in ("omega", "prior", "A", "centres")}
+    arr["covars"] = np.ascontiguousarray(
+        np.stack([np.asarray(h["covars"], dtype=np.float64) + add for h in h3ms]))
+    arr["emit_vcounts"] = np.zeros((R, K, S))
+    want = dict(omega=(R, K), prior=(R, K, S), A=(R, K, S, S), centres=(R, K, S, d),
+                covars=(R, K, S, d, d) if covmode == COV_FULL else (R, K, S, d))
+    for k, shp in want.items():
+        if arr[k].shape != shp:
+            raise ValueError(f"the trials' {k} must have shape {shp[1:]}")
+    mix = _capi.VhemMixTrialsT(K, S, d, covmode, *(arr[k].ctypes.data for k in (
+        "omega", "prior", "A", "centres", "covars", "emit_vcounts")))
+    copt = _capi.VhemEmOptT(inf_norm, float(opt["smooth"]), reg, float(opt["termvalue"]), T,
+                            max_iter, int(opt.get("min_iter", 0)))
+    lib = _capi.lib()
+    nb = int(lib.vhem_em_trials_workspace_bytes(ctypes.byref(engine._bt), K, S, R, T))
+    if nb == 0:
+        raise _capi.VbhemError(
+            f"vhem_em_trials_workspace_bytes: unsupported shape (R={R}, K={K}, S={S}, d={d}, "
+            f"Sb={base.SB}): needs R*K <= 256, Sb <= S <= 16, d <= 16")
+    ws = getattr(engine, "_em_ws", None)
+    if ws is None or ws.numel() < nb:
+        ws = engine._em_ws = torch.empty((nb,), dtype=torch.uint8, device=engine.device)
+    SL = host.stats_len(K, S, d, covmode)
+    LogLs = np.zeros((R, max_iter + 2))
+    num_iter, fb, fb_iter = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    LogL, stats = np.zeros(R), np.zeros((R, SL))
+    rc = lib.vhem_em_run_trials(ctypes.byref(engine._bt), _capi.ptr(Ni), _capi.ptr(omegaB), R, T,
+                                ctypes.byref(copt), ctypes.byref(mix), LogLs.ctypes.data,
+                                num_iter.ctypes.data, LogL.ctypes.data, fb.ctypes.data,
+                                fb_iter.ctypes.data, stats.ctypes.data, _capi.ptr(engine.hatZ),
+                                _capi.ptr(engine.LL), _capi.ptr(ws), ws.numel(), engine._stream())
+    _capi.check(rc, "vhem_em_run_trials")
+    flagged = [r for r in range(R) if fb[r]]
+    Z = engine.hatZ.cpu().numpy()
+    Lel = engine.LL.cpu().numpy()
+    hs: List[Optional[dict]] = [None] * R
+    for r in range(R):
+        if fb[r]:
+            continue
+        n, cols = int(num_iter[r]), slice(r * K, (r + 1) * K)
+        hs[r] = dict(omega=arr["omega"][r].copy(), prior=arr["prior"][r].copy(), A=arr["A"][r].copy(),
+                     centres=arr["centres"][r].copy(), covars=arr["covars"][r].copy(),
+                     emit_vcounts=arr["emit_vcounts"][r].copy(), LogL=float(LogL[r]),
+                     LogLs=[float(x) for x in LogLs[r, :n + 1]], Z=Z[:, cols].copy(),
+                     L_elbo1=Lel[:, cols] / inf_norm, num_iter=n)
+    if flagged:
+        # the degenerate fixes draw from the trial's own Generator: the unchanged host
+        # loop, from the initial mixtures, on a fresh engine of that many trials
+        eng = EStepEngine(base, len(flagged) * K, S, T, device=engine.device, trials=len(flagged))
+        redo = hem_h3m_c_trials([h3ms[r] for r in flagged], eng, opt, [rngs[r] for r in flagged])
+        for r, h in zip(flagged, redo):
+            hs[r] = h
+    for h in hs:
+        h["fallback_trials"] = list(flagged)
+    return hs
+
+
+def hem_h3m_c_trials(h3ms: List[dict], engine, opt: dict, rngs=None,
+                     em_engine: str = "host") -> List[dict]:
     """hem_h3m_c_step.m for R initialisations at once: one batched fused E-step per
     iteration (vhem_estep_fused_trials); a trial that has stopped keeps its final
     state while its clusters ride along (as em.vbhem_h3m_c_trials).  ``rngs``: one
     numpy Generator per trial for the degenerate fixes' rand.  Returns the R final
-    mixtures with Z, LogL, LogLs, L_elbo1, num_iter."""
+    mixtures with Z, LogL, LogLs, L_elbo1, num_iter.
+
+    em_engine: ``"host"`` (the default) runs the stopping rule, the M-step and the next
+    E-step constants of every trial in numpy between two launches.  ``"device"`` keeps
+    the loop on the GPU (vhem_em_run_trials: a device :class:`EStepEngine`, R K <= 256,
+    Sb <= S <= 16, d <= 16, min_iter <= max_iter + 1; :func:`device_em_supported`).  The
+    device draws no random number: a trial that needs a degenerate fix, or turns
+    non-finite, is frozen there and flagged, and is then rerun by the host loop from its
+    initial mixture with its own untouched Generator, so every trial's result is the
+    host engine's.  Every dict returned by the device engine carries
+    ``fallback_trials``: the indices (into ``h3ms``) of the trials that were rerun."""
+    if em_engine not in ("host", "device"):
+        raise ValueError(f"em_engine {em_engine!r}: 'host' or 'device'")
     R = len(h3ms)
     if engine.trials != R:
         raise ValueError("engine.trials must equal len(h3ms)")
+    if em_engine == "device":
+        rngs = rngs if rngs is not None else [np.random.default_rng(0) for _ in range(R)]
+        return _hem_h3m_c_trials_device(h3ms, engine, opt, rngs)
     base = engine.base
     covmode = base.covmode
     Kb, d = base.N, base.d
@@ -410,7 +520,10 @@ def hem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
               inits: Optional[List[dict]] = None) -> dict:
     """hem_h3m_c.m ('base', 'baseem', 'gmmNew', 'gmmNew2'): ``trials`` EM runs, trial t
     seeded seed + t, batched in launches of at most MAX_BATCH_CLUSTERS clusters; the
-    best LogL wins (MATLAB's max skips NaN).  K == Kb returns the base mixture
+    best LogL wins (MATLAB's max skips NaN).  opt['em_engine'] = 'device' keeps the EM
+    loop of every chunk inside the device engine's shapes on the GPU
+    (:func:`hem_h3m_c_trials`); any other chunk takes the host engine, with either
+    setting.  K == Kb returns the base mixture
     (:19-25).  Every trial NaN raises ValueError (the reference's redo ladder,
     :304-320, is reduced to that).  ``inits``: the trials' initial mixtures (skips the
     initialisation)."""
@@ -428,10 +541,15 @@ def hem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     make = engine_factory or _device_engine(device)
     outs: List[dict] = []
     per = max(1, MAX_BATCH_CLUSTERS // K) if (S <= 16 and base.SB <= S) else 1
+    from .estep import EStepEngine
+    want_device = opt.get("em_engine", "host") == "device"
     for r0 in range(0, R, per):
         chunk = inits[r0:r0 + per]
         eng = make(base, len(chunk) * K, S, int(opt["tau"]), trials=len(chunk))
-        outs.extend(hem_h3m_c_trials(chunk, eng, opt, rngs[r0:r0 + per]))
+        on_device = (want_device and isinstance(eng, EStepEngine)
+                     and device_em_supported(base, K, S, len(chunk), opt))
+        outs.extend(hem_h3m_c_trials(chunk, eng, opt, rngs[r0:r0 + per],
+                                     em_engine="device" if on_device else "host"))
         del eng
     all_LL = np.array([o["LogL"] for o in outs], dtype=float)
     ok = np.isfinite(all_LL) | (all_LL == np.inf)
