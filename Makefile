@@ -5,10 +5,10 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function
 LIBDIR   := $(PKG)/lib
-SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_resp.hip $(PKG)/csrc/vbhem_stats_dense.hip $(PKG)/csrc/vbhem_stats_gated.hip $(PKG)/csrc/vbhem_stats_mfma.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_estep_sched.hip $(PKG)/csrc/vbhem_estep_host.hip $(PKG)/csrc/vbhem_timing.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_em_trials.hip $(PKG)/csrc/vbhem_em_trials_derivs.hip $(PKG)/csrc/vhem_em.hip $(PKG)/csrc/vhem_em_trials.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_kld.hip $(PKG)/csrc/vbhmm_dic.hip $(PKG)/csrc/vbhmm_em.hip $(PKG)/csrc/vbhmm_gmm.hip $(PKG)/csrc/vbhem_wtk.hip $(PKG)/csrc/vbhem_ghem.hip
-HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_estep_plan.h $(PKG)/csrc/vbhem_stats_plan.h $(PKG)/csrc/vbhem_stats_dev.h $(PKG)/csrc/vbhem_estep_sched.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_list4_slots.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_em_iter_body.h $(PKG)/csrc/vbhem_em_trial_ctrl.h $(PKG)/csrc/vbhem_em_deriv_terms.h $(PKG)/csrc/vbhem_em_host.h include/vhem_em.h $(PKG)/csrc/vhem_em_dev.h $(PKG)/csrc/vhem_em_iter_body.h $(PKG)/csrc/vhem_em_trial_ctrl.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h $(PKG)/csrc/vbhmm_hmmset.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_kld.h $(PKG)/csrc/vbhmm_kld_plan.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h include/vbhmm_em.h $(PKG)/csrc/vbhmm_em_run.h include/vbhmm_gmm.h $(PKG)/csrc/vbhmm_gmm_run.h include/vbhem_init.h $(PKG)/csrc/vbhem_wtk_run.h $(PKG)/csrc/vbhem_ghem_run.h $(PKG)/csrc/vbhem_special.h $(PKG)/csrc/vbhmm_batch_launch.h
+SRCS     := $(PKG)/csrc/vbhem_kernels.hip $(PKG)/csrc/vbhem_fb_split.hip $(PKG)/csrc/vbhem_fb_bwd.hip $(PKG)/csrc/vbhem_fb_bwd4.hip $(PKG)/csrc/vbhem_fb_bwd12.hip $(PKG)/csrc/vbhem_fb_list4.hip $(PKG)/csrc/vbhem_fb_list12.hip $(PKG)/csrc/vbhem_emission.hip $(PKG)/csrc/vbhem_resp.hip $(PKG)/csrc/vbhem_stats_dense.hip $(PKG)/csrc/vbhem_stats_gated.hip $(PKG)/csrc/vbhem_stats_mfma.hip $(PKG)/csrc/vbhem_capi.hip $(PKG)/csrc/vbhem_estep_sched.hip $(PKG)/csrc/vbhem_estep_host.hip $(PKG)/csrc/vbhem_timing.hip $(PKG)/csrc/vbhem_em.hip $(PKG)/csrc/vbhem_em_dev.hip $(PKG)/csrc/vbhem_em_trials.hip $(PKG)/csrc/vbhem_em_trials_derivs.hip $(PKG)/csrc/vhem_em.hip $(PKG)/csrc/vhem_em_trials.hip $(PKG)/csrc/vbhem_rccl.hip $(PKG)/csrc/vbhem_h3m.hip $(PKG)/csrc/vbhmm_fb.hip $(PKG)/csrc/vbhmm_score.hip $(PKG)/csrc/vbhmm_ppk.hip $(PKG)/csrc/vbhmm_ccfd.hip $(PKG)/csrc/vbhmm_kld.hip $(PKG)/csrc/vbhmm_dic.hip $(PKG)/csrc/vbhmm_em.hip $(PKG)/csrc/vbhmm_gmm.hip $(PKG)/csrc/vbhem_wtk.hip $(PKG)/csrc/vbhem_wtk_tiled.hip $(PKG)/csrc/vbhem_ghem.hip
+HDRS     := include/vbhem_estep.h include/vbhem_dist.h include/vbhmm_fb.h $(PKG)/csrc/vbhem_internal.h $(PKG)/csrc/vbhem_estep_plan.h $(PKG)/csrc/vbhem_stats_plan.h $(PKG)/csrc/vbhem_stats_dev.h $(PKG)/csrc/vbhem_estep_sched.h $(PKG)/csrc/vbhem_switches.h $(PKG)/csrc/vbhem_list4_slots.h $(PKG)/csrc/vbhem_math.h $(PKG)/csrc/vbhem_log_table.h include/vbhem_em.h $(PKG)/csrc/vbhem_em_dev.h $(PKG)/csrc/vbhem_em_iter_body.h $(PKG)/csrc/vbhem_em_trial_ctrl.h $(PKG)/csrc/vbhem_em_deriv_terms.h $(PKG)/csrc/vbhem_em_host.h include/vhem_em.h $(PKG)/csrc/vhem_em_dev.h $(PKG)/csrc/vhem_em_iter_body.h $(PKG)/csrc/vhem_em_trial_ctrl.h $(PKG)/csrc/vbhem_exact.h $(PKG)/csrc/vbhem_mfma4.h include/vbhmm_score.h $(PKG)/csrc/vbhmm_score_pair.h $(PKG)/csrc/vbhmm_hmmset.h include/vbhmm_ppk.h $(PKG)/csrc/vbhmm_ppk_pair.h include/vbhmm_ccfd.h $(PKG)/csrc/vbhmm_ccfd_row.h include/vbhmm_kld.h $(PKG)/csrc/vbhmm_kld_plan.h include/vbhmm_dic.h $(PKG)/csrc/vbhmm_dic_pair.h include/vbhmm_em.h $(PKG)/csrc/vbhmm_em_run.h include/vbhmm_gmm.h $(PKG)/csrc/vbhmm_gmm_run.h include/vbhem_init.h $(PKG)/csrc/vbhem_wtk_run.h $(PKG)/csrc/vbhem_wtk_tiled_run.h $(PKG)/csrc/vbhem_ghem_run.h $(PKG)/csrc/vbhem_special.h $(PKG)/csrc/vbhmm_batch_launch.h
 OBJS     := $(patsubst $(PKG)/csrc/%.hip,$(LIBDIR)/%.o,$(SRCS))
-CHECKS   := mathcheck scorecheck ppkcheck ccfdcheck kldcheck plancheck diccheck vbhmmemcheck gmmcheck wtkcheck ghemcheck emtrialscheck emderivcheck vhememcheck
+CHECKS   := mathcheck scorecheck ppkcheck ccfdcheck kldcheck plancheck diccheck vbhmmemcheck gmmcheck wtkcheck wtktilecheck ghemcheck emtrialscheck emderivcheck vhememcheck
 CHECK_HDRS := $(wildcard tests/checklib/*.h)
 
 all: lib oracle mex $(CHECKS)
@@ -36,7 +36,7 @@ $(LIBDIR)/%_mex.so: integration/%_mex.c integration/h3m_mex_common.h include/vbh
 
 # test-only: per check library, host builds of the arithmetic headers the kernels share
 # (vbhem_math.h, vbhmm_score_pair.h, vbhmm_ppk_pair.h, vbhmm_ccfd_row.h, vbhmm_kld_plan.h, vbhem_estep_plan.h, vbhem_stats_plan.h, vbhmm_dic_pair.h,
-# vbhmm_em_run.h, vbhmm_gmm_run.h, vbhem_wtk_run.h, vbhem_ghem_run.h, vbhem_em_trial_ctrl.h, vbhem_em_deriv_terms.h,
+# vbhmm_em_run.h, vbhmm_gmm_run.h, vbhem_wtk_run.h, vbhem_wtk_tiled_run.h, vbhem_ghem_run.h, vbhem_em_trial_ctrl.h, vbhem_em_deriv_terms.h,
 # vhem_em_trial_ctrl.h, vhem_em_iter_body.h) and the library's kernels behind the same calls
 define CHECK_RULE
 $(1): tests/$(1)/lib$(1).so
@@ -47,7 +47,7 @@ endef
 $(foreach c,$(CHECKS),$(eval $(call CHECK_RULE,$(c))))
 
 # test-only, CPU: per routine, the serial walkers (vbhmm_em_run.h, vbhmm_gmm_run.h,
-# vbhem_wtk_run.h, vbhem_ghem_run.h), the EM trials' stopping rules (vbhem_em_trial_ctrl.h,
+# vbhem_wtk_run.h, vbhem_wtk_tiled_run.h, vbhem_ghem_run.h), the EM trials' stopping rules (vbhem_em_trial_ctrl.h,
 # vhem_em_trial_ctrl.h), the VHEM M-step body (vhem_em_iter_body.h) and the bound's
 # hyperparameter derivatives (vbhem_em_deriv_terms.h) in a stand-alone
 # program under the address and undefined-behaviour sanitizers (not part of `all`, not run by pytest)
@@ -59,6 +59,7 @@ endef
 $(eval $(call SANITIZE_RULE,vbhmmem,vbhmmemcheck))
 $(eval $(call SANITIZE_RULE,gmm,gmmcheck))
 $(eval $(call SANITIZE_RULE,wtk,wtkcheck))
+$(eval $(call SANITIZE_RULE,wtktile,wtktilecheck))
 $(eval $(call SANITIZE_RULE,ghem,ghemcheck))
 $(eval $(call SANITIZE_RULE,emtrials,emtrialscheck))
 $(eval $(call SANITIZE_RULE,emderiv,emderivcheck))
@@ -71,7 +72,7 @@ kld_sanitize: tests/kldcheck/walker_main.cpp $(HDRS) $(CHECK_HDRS)
 	tests/kldcheck/walker_sanitize
 
 clean:
-	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so $(foreach c,$(CHECKS),tests/$(c)/lib$(c).so) tests/vbhmmemcheck/walker_sanitize tests/gmmcheck/walker_sanitize tests/wtkcheck/walker_sanitize tests/ghemcheck/walker_sanitize tests/kldcheck/walker_sanitize tests/emtrialscheck/walker_sanitize tests/emderivcheck/walker_sanitize tests/vhememcheck/walker_sanitize
+	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/mxshim/libmxshim.so $(foreach c,$(CHECKS),tests/$(c)/lib$(c).so) tests/vbhmmemcheck/walker_sanitize tests/gmmcheck/walker_sanitize tests/wtkcheck/walker_sanitize tests/wtktilecheck/walker_sanitize tests/ghemcheck/walker_sanitize tests/kldcheck/walker_sanitize tests/emtrialscheck/walker_sanitize tests/emderivcheck/walker_sanitize tests/vhememcheck/walker_sanitize
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle mex $(CHECKS) vbhmmem_sanitize gmm_sanitize wtk_sanitize ghem_sanitize kld_sanitize emtrials_sanitize emderiv_sanitize vhemem_sanitize clean
+.PHONY: all lib oracle mex $(CHECKS) vbhmmem_sanitize gmm_sanitize wtk_sanitize wtktile_sanitize ghem_sanitize kld_sanitize emtrials_sanitize emderiv_sanitize vhemem_sanitize clean

@@ -262,6 +262,10 @@ EXPORTS = {
     "vbhem_wtk_states_workspace_bytes": (_c_size, [ctypes.c_longlong]),
     "vbhem_wtk_states_batch": (_c_int, [_c_int] * 5 + [_vp, _vp, _c_int] + [_vp] * 4 + [ctypes.c_longlong]
                                + [_vp] * 6 + [_c_size, _vp]),
+    "vbhem_wtk_cluster_tiled_workspace_bytes": (_c_size, [_c_int] * 5),
+    "vbhem_wtk_cluster_tiled_batch": (_c_int, [_c_int] * 4 + [_vp] * 4 + [_c_int] + [_vp] * 5 + [_c_size, _vp]),
+    "vbhem_wtk_seed_tiled_workspace_bytes": (_c_size, [_c_int] * 5),
+    "vbhem_wtk_seed_tiled_batch": (_c_int, [_c_int] * 4 + [_vp] * 3 + [_c_int] + [_vp] * 4 + [_c_size, _vp]),
     "vbhem_ghem_workspace_bytes": (_c_size, [_c_int] * 6),
     "vbhem_ghem_fit_batch": (_c_int, [_c_int] * 5 + [_vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _vp, _c_int]
                              + [_vp] * 8 + [_c_size, _vp]),

@@ -23,7 +23,11 @@ another in numpy), 'gmmNew' (vbhemhmm_init.m:103-293: the base
 Gaussians reduced by hierarchical EM, GMM_MixHierEM.m, h3m.gmmnew_init; with
 opt['init_engine'] = 'device' every trial's EM in one batched device call,
 h3m.gmmnew_init_batch), or 'auto'
-(vbhem_h3m_cluster.m:359-395: each of the three, the best bound wins).
+(vbhem_h3m_cluster.m:359-395: each of the three, the best bound wins).  Under
+opt['init_engine'] = 'device', opt['init_schedule'] picks how the k-means of both
+initialisations is laid out on the GPU: 'block' (the default) one workgroup per trial,
+'tiled' every pass of every trial over a grid of point tiles; 'auto'
+uses it for both; under 'host' it has no effect.
 
 The EM of the trials (opt['em_engine']): 'host' (the default) batches the E-step and
 runs the rest of an iteration in numpy, trial by trial; 'device' keeps the whole loop
@@ -100,6 +104,12 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
     # and the hierarchical EM of every 'gmmNew' trial (h3m.gmmnew_init_batch) in batched
     # device calls; 'baseem' has no device path and runs on the host
     batched = init_engine == "device" and initmode in ("wtkmeans", "gmmNew")
+    # init_schedule (read under init_engine='device' only): 'block' (the default) gives every
+    # trial's k-means to one workgroup; 'tiled' spreads every pass of every trial over the
+    # whole device (csrc/vbhem_wtk_tiled.hip)
+    init_schedule = opt.get("init_schedule", "block")
+    if init_schedule not in ("block", "tiled"):
+        raise ValueError(f"init_schedule {init_schedule!r}: 'block' or 'tiled'")
     # em_engine='device': the EM of every chunk of trials stays on the device
     # (native_em.run_trials); the default 'host' runs its per-iteration math in numpy
     em_engine = opt.get("em_engine", "host")
@@ -112,7 +122,8 @@ def vbhem_h3m_c(base: BaseSet, opt: dict, device="cuda", engine_factory=None,
         raise ValueError(f"hyp_engine {hyp_engine!r}: 'host' or 'device'")
     if batched:
         init_batch =wtkmeans_init_batch if initmode == "wtkmeans" else gmmnew_init_batch
-        posts = init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device)
+        posts = init_batch(base, opt, [int(opt["seed"]) + it for it in range(1, R + 1)], device,
+                           **(dict(schedule="tiled") if init_schedule == "tiled" else {}))
     pts = wtkmeans_points(base, opt.get("initopt_mode", "r0")) if initmode == "wtkmeans" and not batched else None
     if initmode == "gmmNew" and not batched:
         bn = base.numpy()

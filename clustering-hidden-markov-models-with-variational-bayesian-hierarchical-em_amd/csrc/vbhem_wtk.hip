@@ -14,6 +14,10 @@
 // fits 256 VGPRs without scratch), and the threads' sums are added in a fixed tree.  No
 // atomics; every loop is bounded by n, K, S, d or the iteration limits.  A trial that is not OK writes its status alone: labels are
 // worked on in the workspace and copied out at the end.
+//
+// This is the BLOCK schedule.  The tiled schedule (vbhem_wtk_tiled.hip) launches
+// wtk_cluster_kernel through wtk_block_rerun for the trials whose Lloyd update emptied a
+// cluster: the kernel then reads a per-trial flag first and leaves where it is clear.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +27,7 @@
 #include "vbhem_init.h"
 #include "vbhem_internal.h"
 #include "vbhem_wtk_run.h"
+#include "vbhem_wtk_tiled_run.h"
 
 namespace vbhem {
 namespace {
@@ -36,12 +41,17 @@ struct ClusterArgs {
   int *labels, *counts, *status, *iters;
   double *wd;  // [chunk][n]
   int *wl;     // [chunk][n]
+  // the tiled schedule's re-seed hand-over (vbhem_wtk_tiled.hip): a workgroup whose trial's
+  // flag only[block * only_stride] is clear leaves at once; null: every trial runs
+  const int *only;
+  int only_stride;
 };
 
 template <int DB>
 __global__ __launch_bounds__(kBlock) void wtk_cluster_kernel(const ClusterArgs p) {
   __shared__ Block<DB> b;
   const int tid = threadIdx.x, r = p.R0 + blockIdx.x, n = p.n, d = p.d, K = p.K;
+  if (p.only && !p.only[(size_t)blockIdx.x * p.only_stride]) return;
   double *dwork = p.wd + (size_t)blockIdx.x * n;
   int *lwork = p.wl + (size_t)blockIdx.x * n;
   const int j0 = p.j0[r];
@@ -117,6 +127,18 @@ int chunk_of(int chunk_trials, int n, int R) {
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(R, 1), fit));
 }
 
+int launch_cluster(const ClusterArgs &a, int trials, hipStream_t st) {
+  const dim3 grid((unsigned)trials), block(kBlock);
+  switch (dim_bucket(a.d)) {
+    case 2: hipLaunchKernelGGL(wtk_cluster_kernel<2>, grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL(wtk_cluster_kernel<4>, grid, block, 0, st, a); break;
+    case 8: hipLaunchKernelGGL(wtk_cluster_kernel<8>, grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL(wtk_cluster_kernel<16>, grid, block, 0, st, a); break;
+  }
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, "wtk_cluster_kernel") : VBHEM_OK;
+}
+
 int check_sizes(const char *what, int n, int d, int K, int S, int R) {
   if (n < 1 || d < 1 || K < 1 || S < 1 || R < 0)
     return set_error(VBHEM_ERR_ARG, std::string(what) + ": need n, d, K, S >= 1 and R >= 0");
@@ -127,6 +149,20 @@ int check_sizes(const char *what, int n, int d, int K, int S, int R) {
 }
 
 }  // namespace
+
+// The block schedule over the trials R0 .. R0 + trials - 1 whose flag is set (see
+// ClusterArgs::only), from scratch, for the tiled schedule's emptied-cluster trials.
+int wtk_block_rerun(int n, int d, int K, int R0, int trials, const double *x, const double *w, const int *j0,
+                    const double *u, int *labels, int *counts, int *status, int *iters, double *wd, int *wl,
+                    const int *only, int only_stride, hipStream_t st) {
+  ClusterArgs a{};
+  a.R0 = R0; a.n = n; a.d = d; a.K = K; a.ustride = std::max(K - 1, 1);
+  a.x = x; a.w = w; a.u = u; a.j0 = j0;
+  a.labels = labels; a.counts = counts; a.status = status; a.iters = iters;
+  a.wd = wd; a.wl = wl; a.only = only; a.only_stride = only_stride;
+  return launch_cluster(a, trials, st);
+}
+
 }  // namespace vbhem
 
 extern "C" {
@@ -161,15 +197,8 @@ int vbhem_wtk_cluster_batch(int n, int d, int K, int R, const double *x_dev, con
   hipStream_t st = static_cast<hipStream_t>(stream);
   for (int r0 = 0; r0 < R; r0 += chunk) {
     a.R0 = r0;
-    const dim3 grid((unsigned)std::min(chunk, R - r0)), block(kBlock);
-    switch (dim_bucket(d)) {
-      case 2: hipLaunchKernelGGL(wtk_cluster_kernel<2>, grid, block, 0, st, a); break;
-      case 4: hipLaunchKernelGGL(wtk_cluster_kernel<4>, grid, block, 0, st, a); break;
-      case 8: hipLaunchKernelGGL(wtk_cluster_kernel<8>, grid, block, 0, st, a); break;
-      default: hipLaunchKernelGGL(wtk_cluster_kernel<16>, grid, block, 0, st, a); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "wtk_cluster_kernel");
+    const int lrc = launch_cluster(a, std::min(chunk, R - r0), st);
+    if (lrc != VBHEM_OK) return lrc;
   }
   return VBHEM_OK;
 }

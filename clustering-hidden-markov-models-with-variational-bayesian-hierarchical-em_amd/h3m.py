@@ -500,6 +500,16 @@ def _wtk_posterior(opt: dict, mode: str, Kb: int, d: int, covmode: int, centres:
 # ----------------------------------------------------------------------------
 WTK_OK, WTK_DEGENERATE, WTK_BAD = 0, 1, 2
 WTK_MAX_DIM, WTK_MAX_K, WTK_MAX_S = 16, 32, 16
+# how the k-means of the batched initialisations is laid out on the device: 'block' gives a
+# trial to one workgroup; 'tiled' spreads every pass of every trial over a grid of point
+# tiles (csrc/vbhem_wtk_tiled.hip)
+INIT_SCHEDULES = ("block", "tiled")
+
+
+def _init_schedule(schedule) -> str:
+    if schedule not in INIT_SCHEDULES:
+        raise ValueError(f"schedule {schedule!r}: 'block' or 'tiled'")
+    return schedule
 
 
 def wtkmeans_points_batched(base: BaseSet, mode: str = "r0", device=None):
@@ -536,11 +546,14 @@ def wtkmeans_points_batched(base: BaseSet, mode: str = "r0", device=None):
 
 class WtkDeviceEngine:
     """The two batched calls of include/vbhem_init.h on one device.  ``cluster`` keeps the
-    trials' labels on the device for ``states``; ``labels_of`` fetches one trial's."""
+    trials' labels on the device for ``states``; ``labels_of`` fetches one trial's.
+    ``schedule``: 'block' (one workgroup per trial) or 'tiled' (vbhem_wtk_cluster_tiled_batch)
+    for ``cluster``; ``states`` is the same under both."""
 
-    def __init__(self, device, chunk_trials=None):
+    def __init__(self, device, chunk_trials=None, schedule="block"):
         self.dev = torch.device(device)
         self.chunk = int(chunk_trials or 0)
+        self.schedule = _init_schedule(schedule)
 
     def cluster(self, pts, w, K, j0, u):
         """pts [n][d], w [n] on the device; j0 [R], u [R][max(K-1, 1)] numpy.  Returns
@@ -556,12 +569,13 @@ class WtkDeviceEngine:
         counts = torch.zeros((R, K), dtype=torch.int32, device=dev)
         status = torch.full((R,), -1, dtype=torch.int32, device=dev)
         iters = torch.zeros((R, 2), dtype=torch.int32, device=dev)
-        wb = lib.vbhem_wtk_cluster_workspace_bytes(n, d, K, R, self.chunk)
+        name = "vbhem_wtk_cluster_tiled" if self.schedule == "tiled" else "vbhem_wtk_cluster"
+        wb = getattr(lib, name + "_workspace_bytes")(n, d, K, R, self.chunk)
         ws = _capi.workspace(wb, dev, 16)
         p = _capi.ptr
-        _capi.check(lib.vbhem_wtk_cluster_batch(n, d, K, R, p(pts), p(w), p(tj), p(tu), self.chunk, p(labels),
-                                                p(counts), p(status), p(iters), p(ws), ws.numel(),
-                                                _capi.stream(dev)), "vbhem_wtk_cluster_batch")
+        _capi.check(getattr(lib, name + "_batch")(n, d, K, R, p(pts), p(w), p(tj), p(tu), self.chunk, p(labels),
+                                                  p(counts), p(status), p(iters), p(ws), ws.numel(),
+                                                  _capi.stream(dev)), name + "_batch")
         return labels, counts.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
 
     def labels_of(self, labels, r):
@@ -595,7 +609,7 @@ class WtkDeviceEngine:
 
 
 def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_trials=None,
-                        engine=None, info: Optional[dict] = None) -> List[Posterior]:
+                        engine=None, info: Optional[dict] = None, schedule="block") -> List[Posterior]:
     """``[wtkmeans_init(base, opt, s, pts) for s in wtseeds]`` with the k-means of every
     trial in two batched device calls (csrc/vbhem_wtk.hip): all trials' K-way clustering,
     then the S-way k-means of every (trial, cluster) with more than S members.  The host
@@ -605,10 +619,12 @@ def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_
     calls, because the second stage's first draw is an index into the members.  Clusters
     with at most S members and empty clusters are filled in here as wtkmeans_init does;
     a trial whose D2 total vanishes (the host's generator takes another branch there) is
-    replayed through wtkmeans_init.  ``engine``: a stand-in for :class:`WtkDeviceEngine`;
+    replayed through wtkmeans_init.  ``schedule``: 'block' or 'tiled', the first stage's
+    layout on the device (:class:`WtkDeviceEngine`); a given ``engine`` keeps its own.
+    ``engine``: a stand-in for :class:`WtkDeviceEngine`;
     ``info``: a dict that receives the seconds of the parts (points, cluster, states: each
-    ends in a copy back to the host; host: the rest), the number of second-stage items and
-    the replayed trials."""
+    ends in a copy back to the host; host: the rest), the number of second-stage items, the
+    replayed trials and the first stage's statuses and iteration counts."""
     import time
     t0 = time.perf_counter()
     copt = clip_hyps(opt)
@@ -618,7 +634,8 @@ def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_
     for name, val, lim in (("d", d, WTK_MAX_DIM), ("K", K, WTK_MAX_K), ("S", S, WTK_MAX_S)):
         if val > lim:
             raise ValueError(f"wtkmeans_init_batch: {name} = {val} exceeds the device limit {name} <= {lim}")
-    eng = engine if engine is not None else WtkDeviceEngine(device, chunk_trials)
+    _init_schedule(schedule)
+    eng = engine if engine is not None else WtkDeviceEngine(device, chunk_trials, schedule)
     dev = getattr(eng, "dev", torch.device("cpu"))
     pts, w, c11 = wtkmeans_points_batched(base, mode, dev)
     n = int(pts.shape[0])
@@ -631,7 +648,7 @@ def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_
     j0 = np.array([g.integers(n) for g in g1s], dtype=np.int64)
     u = np.array([[g.random() for _ in range(K - 1)] + [0.0] * (K == 1) for g in g1s])
     t2 = time.perf_counter()
-    labels, counts, status, _ = eng.cluster(pts, w, K, j0, u)
+    labels, counts, status, iters1 = eng.cluster(pts, w, K, j0, u)
     t3 = time.perf_counter()
     if (status == WTK_BAD).any():
         raise ValueError("wtkmeans_init_batch: non-finite base-state means or weights")
@@ -676,7 +693,8 @@ def wtkmeans_init_batch(base: BaseSet, opt: dict, wtseeds, device="cuda", chunk_
         posts.append(_wtk_posterior(copt, mode, Kb, d, base.covmode, centres, g2s[r], c11))
     if info is not None:
         total = time.perf_counter() - t0
-        info.update(points=t1 - t0, cluster=t3 - t2, states=t5 - t4, items=len(items), replayed=sorted(replay))
+        info.update(points=t1 - t0, cluster=t3 - t2, states=t5 - t4, items=len(items), replayed=sorted(replay),
+                    status=np.asarray(status), iters=np.asarray(iters1))
         info["host"] = total - info["points"] - info["cluster"] - info["states"]
     return posts
 
@@ -841,10 +859,33 @@ class GhemDeviceEngine:
                     logpost=None if lpost is None else lpost.cpu().numpy(), logp=logp.cpu().numpy(),
                     status=status.cpu().numpy(), iters=iters.cpu().numpy())
 
+    def seed(self, X, T, j0, u):
+        """kmeans_pp alone by the tiled schedule (vbhem_wtk_seed_tiled_batch): X [n][d], j0
+        [R], u [R][T-1] numpy.  Returns (centres [R][T][d], status [R], Lloyd passes [R]) as
+        numpy; only the rows of OK trials are meaningful."""
+        from . import _capi
+        lib, dev = _capi.lib(), self.dev
+        n, d = X.shape
+        R = len(j0)
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+        tx, tj = t(X, np.float64), t(j0, np.int32)
+        tu = t(np.asarray(u, dtype=np.float64).reshape(R, max(T - 1, 1)), np.float64)
+        cen = torch.zeros((R, T, d), dtype=torch.float64, device=dev)
+        status = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        iters = torch.zeros((R,), dtype=torch.int32, device=dev)
+        wb = lib.vbhem_wtk_seed_tiled_workspace_bytes(n, d, T, R, self.chunk)
+        ws = _capi.workspace(wb, dev, 16)
+        p = _capi.ptr
+        _capi.check(lib.vbhem_wtk_seed_tiled_batch(n, d, T, R, p(tx), p(tj), p(tu), self.chunk, p(cen), p(status),
+                                                   p(iters), p(ws), ws.numel(), _capi.stream(dev)),
+                    "vbhem_wtk_seed_tiled_batch")
+        return cen.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
+
 
 def gmm_mix_hier_em_batch(centres: np.ndarray, covars: np.ndarray, full: bool, T: int, virtual_samples: float,
                           iterations: int, seeds, device="cuda", chunk_trials=None, engine=None,
-                          init_centres=None, want_logpost: bool = False, info: Optional[dict] = None):
+                          init_centres=None, want_logpost: bool = False, info: Optional[dict] = None,
+                          schedule="block"):
     """``[gmm_mix_hier_em(centres, covars, full, T, virtual_samples, iterations,
     Generator(PCG64(s))) for s in seeds]`` with the hierarchical EM of every trial in one
     batched device call (csrc/vbhem_ghem.hip); the fourth entry of a trial's tuple is None
@@ -855,7 +896,12 @@ def gmm_mix_hier_em_batch(centres: np.ndarray, covars: np.ndarray, full: bool, T
     centres of every trial, no seeding.  T = 1 is the closed form on the host.  A trial
     whose status is not OK (a vanished D2 total, a logp that is not finite, a failed pivot,
     non-finite points) is replayed through gmm_mix_hier_em with a fresh generator of its
-    seed and behaves as it does there.  ``engine``: a stand-in for
+    seed and behaves as it does there.  ``schedule`` = 'tiled' (without ``init_centres``):
+    the same draws go to the tiled k-means++ seeding (``engine.seed``,
+    vbhem_wtk_seed_tiled_batch) and its centres start the EM call; a trial whose seeding is
+    not OK is replayed like the others (its slot of the EM call gets zero centres and is
+    ignored), and the seeding's Lloyd passes are reported where the EM call's were
+    (``info['seed']``: its seconds).  ``engine``: a stand-in for
     :class:`GhemDeviceEngine`; ``info`` also receives the seconds of the parts (fit: the
     device call and its copies; host: the rest), the statuses, the iteration counts and
     the replayed trials."""
@@ -888,7 +934,20 @@ def gmm_mix_hier_em_batch(centres: np.ndarray, covars: np.ndarray, full: bool, T
             u[r] = [g.random() for _ in range(T - 1)]
     eng = engine if engine is not None else GhemDeviceEngine(device, chunk_trials)
     t1 = time.perf_counter()
-    got = eng.fit(X, C, bool(full), T, float(virtual_samples), int(iterations), j0, u, inits, bool(want_logpost))
+    seeded = None
+    if _init_schedule(schedule) == "tiled" and inits is None:
+        scen, sst, sit = eng.seed(X, T, j0, u)
+        seeded = (np.asarray(sst), np.asarray(sit))
+        start = np.where((seeded[0] == WTK_OK)[:, None, None], scen, 0.0)
+        ts = time.perf_counter()
+        got = eng.fit(X, C, bool(full), T, float(virtual_samples), int(iterations), None, None, start,
+                      bool(want_logpost))
+        got = dict(got, status=np.where(seeded[0] == WTK_OK, got["status"], seeded[0]).astype(np.int32),
+                   iters=np.stack([seeded[1], got["iters"][:, 1]], 1).astype(np.int32))
+    else:
+        ts = t1
+        got = eng.fit(X, C, bool(full), T, float(virtual_samples), int(iterations), j0, u, inits,
+                      bool(want_logpost))
     t2 = time.perf_counter()
     out, replay = [], []
     for r in range(R):
@@ -901,18 +960,20 @@ def gmm_mix_hier_em_batch(centres: np.ndarray, covars: np.ndarray, full: bool, T
                     got["logpost"][r] if want_logpost else None))
     if info is not None:
         info.update(rngs=rngs, replayed=replay, status=got["status"], iters=got["iters"], logp=got["logp"],
-                    fit=t2 - t1)
+                    fit=t2 - t1, seed=ts - t1)
         info["host"] = time.perf_counter() - t0 - info["fit"]
     return out
 
 
 def gmmnew_init_batch(base: BaseSet, opt: dict, seeds, device="cuda", chunk_trials=None, engine=None,
-                      info: Optional[dict] = None) -> List[Posterior]:
+                      info: Optional[dict] = None, schedule="block") -> List[Posterior]:
     """``[gmmnew_init(base, opt, s) for s in seeds]`` with the hierarchical EM of every
     trial in one batched device call (:func:`gmm_mix_hier_em_batch`); the draws after the
     EM come from the trial's generator as gmmnew_init takes them.  ``info`` receives the
-    seconds of the parts (points, fit, host: the rest), the replayed trials and the E-steps
-    every device trial evaluated."""
+    seconds of the parts (points, fit, host: the rest; seed: the part of fit the tiled
+    seeding took), the replayed trials and the E-steps every device trial evaluated.
+    ``schedule``: 'block' or 'tiled', the layout of the k-means++ seeding on the device
+    (:func:`gmm_mix_hier_em_batch`)."""
     import time
     t0 = time.perf_counter()
     copt = clip_hyps(opt)
@@ -932,12 +993,13 @@ def gmmnew_init_batch(base: BaseSet, opt: dict, seeds, device="cuda", chunk_tria
     t1 = time.perf_counter()
     sub = {}
     fits = gmm_mix_hier_em_batch(X, C, full, S, copt["Nv"] * Kb, int(copt.get("initopt_iter", 30)), seeds, device,
-                                 chunk_trials, engine, info=sub)
+                                 chunk_trials, engine, info=sub, schedule=schedule)
     posts = [_gmmnew_posterior(copt, mode, Kb, d, full, cen, cov, g) for (_, cen, cov, _), g in zip(fits, sub["rngs"])]
     if info is not None:
         total = time.perf_counter() - t0
-        info.update(points=t1 - t0, fit=sub["fit"], replayed=sub["replayed"],
-                    esteps=[int(v) for v in sub["iters"][:, 1]] if "iters" in sub else [])
+        info.update(points=t1 - t0, fit=sub["fit"], seed=sub.get("seed", 0.0), replayed=sub["replayed"],
+                    esteps=[int(v) for v in sub["iters"][:, 1]] if "iters" in sub else [],
+                    lloyd=[int(v) for v in sub["iters"][:, 0]] if "iters" in sub else [])
         info["host"] = total - info["points"] - info["fit"]
     return posts
 

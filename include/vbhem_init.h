@@ -69,6 +69,44 @@ int vbhem_wtk_states_batch(int n, int d, int K, int S, int R, const double *x_de
                            void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /*
+ * The TILED schedule of the same k-means (csrc/vbhem_wtk_tiled.hip).  The calls above give
+ * a trial to one workgroup (the BLOCK schedule); these spread every pass of every trial over
+ * a grid of (point tile, group of trials) and let a small per-trial kernel add the tile
+ * partials in tile order and apply the rule, round after round, with no host read.  The
+ * number of launches is fixed by K and the pass caps: 2 ((K - 1) + 100 + 1 + 101) + 2 for the
+ * first entry, 2 ((K - 1) + 100) + 2 for the second, per chunk of trials.
+ *
+ *   vbhem_wtk_cluster_tiled_batch  vbhem_wtk_cluster_batch's arguments, layouts, statuses and
+ *                                  limits
+ *   vbhem_wtk_seed_tiled_batch     kmeans_pp alone over all n points for K centres:
+ *                                  centres[R][K][d], status[R], iters[R] (Lloyd passes); the
+ *                                  start centres of vbhem_ghem_fit_batch's init_centres.
+ *                                  Limits: d <= 16, 2 <= K <= VBHEM_GHEM_MAX_T; beyond:
+ *                                  VBHEM_ERR_UNSUPPORTED (K < 2: VBHEM_ERR_ARG)
+ * Per-point values are the block schedule's bit for bit; the n-term sums run over point
+ * tiles whose size depends on (n, d) only (256 points up to n = 262,144, 1,024 beyond), in
+ * point order inside a tile and in tile order across tiles, so the discrete outputs equal
+ * the block schedule's wherever no decision is within rounding, and a trial's result depends
+ * on its own inputs only -- not on R, its place in the list or chunk_trials (0: as many as
+ * fit VBHEM_WTK_DEFAULT_WORKSPACE bytes).  A trial whose Lloyd update empties a cluster is
+ * computed by the block schedule inside the same call (the re-seed is sequential and rare).
+ * A trial that is not OK writes its status alone.
+ */
+size_t vbhem_wtk_cluster_tiled_workspace_bytes(int n, int d, int K, int R, int chunk_trials);
+
+int vbhem_wtk_cluster_tiled_batch(int n, int d, int K, int R, const double *x_dev, const double *weight_dev,
+                                  const int *j0_dev, const double *u_dev, int chunk_trials, int *labels_dev,
+                                  int *counts_dev, int *status_dev, int *iters_dev, void *workspace_dev,
+                                  size_t workspace_bytes, void *stream);
+
+size_t vbhem_wtk_seed_tiled_workspace_bytes(int n, int d, int K, int R, int chunk_trials);
+
+int vbhem_wtk_seed_tiled_batch(int n, int d, int K, int R, const double *x_dev, const int *j0_dev, const double *u_dev,
+                               int chunk_trials, double *centres_dev /* [R][K][d] */, int *status_dev,
+                               int *iters_dev /* [R]: Lloyd passes */, void *workspace_dev, size_t workspace_bytes,
+                               void *stream);
+
+/*
  * The batched 'gmmNew' initialisation (vbhemhmm_init.m:103-293, GMM_MixHierEM.m as
  * h3m.gmm_mix_hier_em restates it for T >= 2): the mixture of all n base-state Gaussians
  * reduced to T components by hierarchical EM, every TRIAL of a list in one call.  A trial
