@@ -2,7 +2,11 @@
 formulas / vbh3m_remove_empty.m (tests/dic_ref.py) pinned on closed forms, the host build
 of the pair routine (csrc/vbhmm_dic_pair.h through tests/diccheck) against the oracle's
 VHEM E-step, vbhem_amd/dic.py on a stand-in engine (the oracle's L) against the
-restatement, and the workspace bound."""
+restatement, and the workspace bound.
+
+The shapes reach every instance of the GPU kernel, and a guard keeps it so.  The inputs of
+the GPU tests' mixed-wave and many-tile cases are built here too, with the conditions under
+which they can tell a wrong kernel from a right one."""
 import math
 import types
 
@@ -41,7 +45,31 @@ SHAPES = {
     "ragged_bases": (9, 4, 3, 7, True, [[4, 4, 4]], False),
     "mixed_sizes": (5, 3, 2, 5, True, [[2, 4, 3], [1, 5]], False),
     "zero_transition": (5, 3, 2, 6, False, [[3, 3]], True),
+    # the kernel's (cluster-state bucket, base-state bucket) instances the shapes above miss
+    "S8_Sb8": (9, 8, 3, 4, True, [[8, 5], [6]], False),        # (8, 8), mixed sizes
+    "S5_Sb9": (5, 9, 2, 4, False, [[5, 7]], False),            # (8, 16)
+    "S9_Sb3": (5, 3, 2, 4, False, [[9, 12, 16]], False),       # (16, 4), 3 clusters
+    "S16_Sb5": (5, 5, 4, 3, True, [[16, 9]], False),           # (16, 8)
+    "d16_S3": (4, 3, 16, 3, False, [[3, 3]], False),           # the longest block of the 4-bucket
+    "K64": (3, 2, 2, 3, False, [[2] * 64], False),             # kMaxModelClusters in one model
+    # (4, 8) and (4, 16): the edge sweep alone ran them, against the host build only
+    "S3_Sb5": (5, 5, 2, 4, False, [[3, 2]], False),
+    "S3_Sb9": (5, 9, 2, 4, False, [[3, 3]], False),
 }
+
+# The tile, wave and sub-tile sweep of tests/test_dic_gpu.py.  The kernel packs SBP = 4, 8 or
+# 16 lanes per base (the bucket of SB): a wave holds 64 / SBP bases, a pass of the workgroup
+# (a sub-tile) 256 / SBP, a tile 64.  N on both sides of each, per SB ...
+EDGES = {3: [1, 15, 16, 17, 63, 64, 65, 129], 5: [1, 7, 8, 9, 31, 32, 33, 64, 65],
+         9: [1, 3, 4, 5, 15, 16, 17, 64, 65]}
+# ... and the largest cluster size of the models it runs with, one call per entry: the
+# cluster-state buckets 4, 8 and 16.
+EDGE_S = (3, 6, 11)
+
+
+def state_bucket(s):
+    """vbhmm_dic_pair.h's state_bucket, restated."""
+    return 4 if s <= 4 else 8 if s <= 8 else 16
 
 
 def build(name, seed=0):
@@ -64,6 +92,33 @@ def build(name, seed=0):
 def oracle_LL(vo, base, models, pk, T):
     L = dr.oracle_pairs(vo, base, models, T)
     return L, dr.mix(L, pk["model_off"], pk["logw"], pk["scale"])
+
+
+def one_sign(L, pk):
+    """The sign condition under which a sum inherits its terms' relative bound: every
+    subject's mixture LSE of every model has the same sign."""
+    terms = []
+    for g in range(pk["G"]):
+        c0, c1 = pk["model_off"][g], pk["model_off"][g + 1]
+        for i in range(L.shape[0]):
+            terms.append(dr.logtrick([pk["logw"][c] + pk["scale"][g] * L[i][c] for c in range(c0, c1)]))
+    t = np.array(terms)
+    return bool((t < 0).all() or (t > 0).all())
+
+
+def test_shapes_reach_every_bucket_pair():
+    """dic_kernel<SP, SBP> has nine instances, SP the bucket of the largest cluster size of
+    a call and SBP the bucket of SB.  SHAPES on its own and the edge sweep on its own reach
+    all nine, a model of SHAPES has kMaxModelClusters clusters, and a ragged base set has
+    a base that owns all SB states."""
+    nine = {(a, b) for a in (4, 8, 16) for b in (4, 8, 16)}
+    got = {(state_bucket(max(max(sz) for sz in sh[5])), state_bucket(sh[1])) for sh in SHAPES.values()}
+    assert got == nine, sorted(nine - got)
+    assert {(state_bucket(S), state_bucket(Sb)) for S in EDGE_S for Sb in EDGES} == nine
+    assert max(len(sz) for sh in SHAPES.values() for sz in sh[5]) == 64
+    for name, sh in SHAPES.items():
+        if sh[4]:
+            assert build(name)[0]["nstates"].max() == sh[1], name
 
 
 # ----------------------------------------------------------------------------
@@ -145,7 +200,7 @@ def test_host_pairs_match_oracle(dic, check_lib, vo, name):
     ref_L, ref_LL = oracle_LL(vo, base, models, pk, T)
     L, rec = dr.host_pairs(check_lib, base, pk, T)
     print(name, "pairs err", elem_err(L, ref_L), "recomputed", rec)
-    assert np.isfinite(ref_L).all()
+    assert np.isfinite(ref_L).all() and one_sign(ref_L, pk)
     assert elem_err(L, ref_L) < RTOL_PAIRS
     Lx, _ = dr.host_pairs(check_lib, base, pk, T, exact_only=True)   # reference order throughout
     assert elem_err(Lx, ref_L) < RTOL_PAIRS
@@ -176,6 +231,98 @@ def test_underflow_pair_is_recomputed_in_reference_order(dic, check_lib, vo):
     print("underflow L", L.tolist(), "oracle", ref_L.tolist(), "recomputed", rec)
     assert rec >= 1, "the case does not reach the recompute path"
     assert np.isfinite(L).all() and elem_err(L, ref_L) < RTOL_PAIRS
+
+
+# (Sb, N, the two bases that underflow): SBP = 4, 8 and 16.  The second base of a row lies in
+# the second tile (67), in the second sub-tile (37: 32 bases a pass at SBP = 8; 21: 16 a pass
+# at SBP = 16); base 3 at SBP = 16 sits in lanes 48..63 of its wave.
+MIXED_WAVE = [(2, 70, (2, 67)), (5, 70, (2, 37)), (9, 40, (3, 21))]
+# Seeds of the base sets, per Sb: the first from Sb on under which the conditions of
+# mixed_wave_refs hold for both named bases, each in the cluster column of its own redo.
+MIXED_WAVE_SEED = {2: 2, 5: 7, 9: 31}
+
+
+def mixed_wave_case(Sb, N, positions):
+    """underflow_case()'s model against N ordinary one-dimensional bases (random A and prior,
+    centres in [10, 30] between the model's means at 0 and 40, variance 1), and against a
+    copy in which the two bases at `positions` sit on one of the means, as underflow_case()'s
+    do.  Returns (plain base set, modified base set, models, T)."""
+    rng = np.random.default_rng(MIXED_WAVE_SEED[Sb])
+    plain = dict(nstates=np.full(N, Sb, np.int32), prior=rng.dirichlet(np.ones(Sb), size=N),
+                 A=rng.dirichlet(np.ones(Sb), size=(N, Sb)), centres=rng.uniform(10.0, 30.0, (N, Sb, 1)),
+                 covars=np.ones((N, Sb, 1)), covmode=0)
+    mod = dict(plain, centres=plain["centres"].copy())
+    mod["centres"][positions[0], :, 0] = 0.1 * np.arange(Sb)
+    mod["centres"][positions[1], :, 0] = 40.0 - 0.1 * np.arange(Sb)
+    _, models, T = underflow_case()
+    return plain, mod, models, T
+
+
+def redo_columns(dic, check_lib, base, mo, T, p):
+    """The clusters of model `mo` against which base p is recomputed in reference order:
+    the host build on that base alone, one cluster at a time."""
+    one = {k: (v[p:p + 1] if isinstance(v, np.ndarray) else v) for k, v in base.items()}
+    cols = []
+    for c in range(np.asarray(mo["prior"]).shape[0]):
+        pkc = dic.pack_models([{k: np.asarray(mo[k])[c:c + 1] for k in ("prior", "A", "centres", "covars")}])
+        if dr.host_pairs(check_lib, one, pkc, T)[1]:
+            cols.append(c)
+    return cols
+
+
+def mixed_wave_refs(dic, check_lib, vo, Sb, N, positions):
+    """The references of a mixed-wave case, and the conditions without which it would not
+    tell a redo of the two pairs' lanes from a redo of their whole waves.  Exactly the two
+    named bases are recomputed, each against one cluster, and the oracle is finite.  The
+    kernel runs the reference-order sweep only for that cluster, so in the wave of each
+    named base (64 / SBP consecutive bases) an ordinary base must have, in that cluster's
+    column, a reference-order L that differs in bits from its factorised L."""
+    plain, mod, models, T = mixed_wave_case(Sb, N, positions)
+    pk = dic.pack_models(models)
+    ref_L, ref_LL = oracle_LL(vo, mod, models, pk, T)
+    assert np.isfinite(ref_L).all() and one_sign(ref_L, pk)
+    host_L, rec = dr.host_pairs(check_lib, mod, pk, T)
+    plain_L, rec_plain = dr.host_pairs(check_lib, plain, pk, T)
+    assert rec == 2 and rec_plain == 0, (rec, rec_plain)
+    exact_plain, _ = dr.host_pairs(check_lib, plain, pk, T, exact_only=True)
+    per_wave = 64 // state_bucket(Sb)
+    differs = exact_plain != plain_L
+    for p in positions:
+        cols = redo_columns(dic, check_lib, mod, models[0], T, p)
+        assert len(cols) == 1, (p, cols)
+        mates = [q for q in range(N) if q // per_wave == p // per_wave and q not in positions]
+        assert differs[mates, cols[0]].any(), (p, cols, mates)
+    exact_mod, _ = dr.host_pairs(check_lib, mod, pk, T, exact_only=True)
+    return plain, mod, pk, T, ref_L, ref_LL, host_L, exact_mod
+
+
+@pytest.mark.parametrize("Sb,N,positions", MIXED_WAVE)
+def test_mixed_wave_case_is_sensitive(dic, check_lib, vo, Sb, N, positions):
+    _, _, _, _, ref_L, _, host_L, exact_mod = mixed_wave_refs(dic, check_lib, vo, Sb, N, positions)
+    print("mixed wave", Sb, "host vs oracle", elem_err(host_L, ref_L), "exact", elem_err(exact_mod, ref_L))
+    assert elem_err(host_L, ref_L) < RTOL_PAIRS and elem_err(exact_mod, ref_L) < RTOL_PAIRS
+
+
+def many_tiles_case(N=16385):
+    """One-state, one-dimensional bases, T = 2, and two models (K = 1, S = 1; K = 2, S = 2
+    with unequal weights): the smallest shape at which dic_reduce_kernel's lanes add more
+    than one tile each (N > 256 tiles of 64)."""
+    rng = np.random.default_rng(16385)
+    base = dict(nstates=np.ones(N, np.int32), prior=np.ones((N, 1)), A=np.ones((N, 1, 1)),
+                centres=rng.uniform(0.0, 5.0, (N, 1, 1)), covars=rng.uniform(0.5, 1.5, (N, 1, 1)), covmode=0)
+    models = [dict(make_reduced(1, 1, 1, 0, seed=600), scale=1.3),
+              dict(make_reduced(2, 2, 1, 0, seed=601), omega=np.array([0.3, 0.7]), scale=0.8)]
+    return base, models, 2
+
+
+def test_many_tiles_case_host_matches_oracle(dic, check_lib, vo):
+    base, models, T = many_tiles_case()
+    pk = dic.pack_models(models)
+    ref_L, ref_LL = oracle_LL(vo, base, models, pk, T)
+    L, rec = dr.host_pairs(check_lib, base, pk, T)
+    assert rec == 0 and np.isfinite(ref_L).all() and one_sign(ref_L, pk)
+    assert elem_err(L, ref_L) < RTOL_PAIRS
+    assert elem_err(dr.host_mix(check_lib, L, pk), ref_LL) < RTOL_PAIRS
 
 
 def test_nan_constant_reaches_only_its_pairs(dic, check_lib):
