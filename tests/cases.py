@@ -175,6 +175,42 @@ TRIAL_COUNT_SHAPES = [
 ]
 
 
+# the observation dimensions d <= 16 that the shapes above leave out (same tuple layout;
+# tests/test_dimension_cases.py, test_fused_dimensions_gpu.py).  By d and the
+# covariance mode the E-step picks: the emission GEMM's k-steps kq = ceil(KD / 4), KD = d (d + 1)
+# / 2 + d (full) or 2 d (diagonal), in register buckets of 4, 12 and 40 k-steps; the feature
+# tiles nt = ceil(NU / 16), NU = 1 + KD, of stats_list_m_kernel<NTW, G> (nt <= 4: G = 4 pair
+# groups of NTW = nt tiles; 5-6: G = 2, NTW = 3; 7-8: G = 2, NTW = 4; 9-12: G = 1, NTW = 3) and,
+# behind the switches, the grouped kernel (NU <= 32), the operand kernel (NU <= 64) and the
+# covariance gather.  Small otherwise: N = 37 ragged bases, K = 4, S = Sb = 3, T = 5
+DIMENSION_SHAPES = [
+    ("d1_full", 37, 4, 3, 3, 1, 1, 5, True),        # kq = 1 of a full covariance (KD = 2), NU = 3
+    ("d6_full", 37, 4, 3, 3, 6, 1, 5, True),        # kq = 7, 12-step bucket; NU = 28, (nt, G, NTW) = (2, 4, 2)
+    ("d7_full", 37, 4, 3, 3, 7, 1, 5, True),        # kq = 9; NU = 36, (3, 4, 3)
+    ("d9_full", 37, 4, 3, 3, 9, 1, 5, True),        # kq = 14: first of the 40-step bucket; NU = 55, (4, 4, 4)
+    ("d10_full", 37, 4, 3, 3, 10, 1, 5, True),      # kq = 17; NU = 66, (5, 2, 3): the second tile group half padded
+    ("d11_full", 37, 4, 3, 3, 11, 1, 5, True),      # kq = 20; NU = 78, (5, 2, 3)
+    ("d12_full", 37, 4, 3, 3, 12, 1, 5, True),      # kq = 23; NU = 91, (6, 2, 3)
+    ("d13_full", 37, 4, 3, 3, 13, 1, 5, True),      # kq = 26; NU = 105, (7, 2, 4): the second tile group partial
+    ("d14_full", 37, 4, 3, 3, 14, 1, 5, True),      # kq = 30; NU = 120, (8, 2, 4)
+    ("d15_full", 37, 4, 3, 3, 15, 1, 5, True),      # kq = 34; NU = 136, (9, 1, 3): the fourth tile group empty
+    ("d6_diag", 37, 4, 3, 3, 6, 0, 5, True),        # kq = 3 (the raw kernel's kq = 3 under NO_UGEMM); NU = 13
+    ("d7_diag", 37, 4, 3, 3, 7, 0, 5, True),        # kq = 4, NU = 15: last of the 4-step bucket and of one tile
+    ("d8_diag", 37, 4, 3, 3, 8, 0, 5, True),        # kq = 4; NU = 17: first of two tiles
+    ("d9_diag", 37, 4, 3, 3, 9, 0, 5, True),        # kq = 5: first of the 12-step bucket; NU = 19
+    ("d15_diag", 37, 4, 3, 3, 15, 0, 5, True),      # kq = 8; NU = 31
+    # K S = 132 > 128 in the 40-step bucket: W' of 256 rows is staged in four chunks of 4 row tiles
+    ("d11_rows", 37, 33, 4, 4, 11, 1, 5, True),
+    # S = 8, T = 10 (fb_bwd4_kernel / fb_list4_kernel): the list-4 accumulation with two feature
+    # tiles of a full covariance; and NU = 55 past the accumulation's 48, where the statistics
+    # fall to stats_list_m_kernel<4, 4> behind fb_list4_kernel (padded base states)
+    ("d6_S8", 37, 4, 8, 8, 6, 1, 10, False),
+    ("d9_S8_ragged", 37, 4, 8, 6, 9, 1, 10, True),
+    # S = 12 (fb_bwd12_kernel / fb_list12_kernel) on the 40-step emission GEMM
+    ("d10_S12", 37, 4, 12, 9, 10, 1, 10, True),
+]
+
+
 def make_reduced(K=3, S=3, d=2, covmode=1, seed=0, zero_transition=False) -> dict:
     """Point-estimate reduced HMMs for the VHEM sibling (hem_hmm_bwd_fwd_mex.c):
     Dirichlet rows for A and prior, means in [0, 5]^d, SPD covariances

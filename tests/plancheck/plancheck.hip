@@ -3,7 +3,7 @@
 // plan_fb, of the epilogue's responsibility / dense / gated plans, and the block-count
 // rules as integers, so the geometry and the choice of kernel are checked on a machine
 // without a GPU (tests/test_estep_plan.py and tests/test_stats_plan.py compare them with
-// recorded tables).
+// recorded tables; tests/test_dimension_cases.py reads the emission GEMM's plan per dimension).
 #include <hip/hip_runtime.h>
 
 #include "vbhem_estep_plan.h"
@@ -117,6 +117,28 @@ void plancheck_stats_gated(int K, int S, int SB, int d, int covmode, int opnd, i
 void plancheck_list4_reduce(int K, int S, int d, int covmode, long long *out) {
   const StatsShape s{K, K, S, S, d, covmode, emission_kdp(d, covmode), true, true, false};
   gated_out(plan_list4_reduce(s), K, 0, Switches{}, out);
+}
+
+// ---- the emission GEMM on the prepared operand (plan_emission_u, csrc/vbhem_emission.hip) ----
+// out [8]: k-steps emission_kdp / 4, W' rows emission_ksp(K S), then plan_emission_u's ok,
+// register bucket ukqb, row tiles per W' chunk urc, chunks (ksp / 16 / urc), waves per
+// block, dynamic LDS (zeros from ok on: past kUMaxKq k-steps, the raw / generic kernels)
+void plancheck_emission(int K, int S, int d, int covmode, long long *out) {
+  EmissionArgs a{};
+  a.K = K; a.S = S; a.d = d; a.covmode = covmode;
+  a.kdp = emission_kdp(d, covmode);
+  a.ksp = emission_ksp(K * S);
+  size_t lds = 0;
+  const bool ok = plan_emission_u(a, lds);
+  const long long v[8] = {a.kdp / 4, a.ksp, ok, a.ukqb, a.urc, ok ? a.ksp / 16 / a.urc : 0, a.nwave,
+                          (long long)lds};
+  for (int k = 0; k < 8; ++k) out[k] = k < 2 || ok ? v[k] : 0;
+}
+
+// may fb_list4_kernel accumulate the gated sums itself (S = 8, T = 10, at most three feature
+// tiles), with list4_stats_reduce_kernel behind it?
+int plancheck_list4_acc(int K, int S, int SB, int T, int d, int covmode) {
+  return list4_acc_supported(S, SB, T, K, us_nu(d, covmode));
 }
 
 long long plancheck_stats_m_blocks(long long resident, int K, int cap, long long su_blocks) {

@@ -75,8 +75,12 @@ def near_reduced(K, S, d, cov, seed):
 def fused_case(name):
     """(base dict, BaseSet, reduced mixture, options, the restatement's E-step and its
     packed statistics) -- computed once, shared by the tests, never modified."""
-    S, Sb, d, cov, ragged, T, K, smooth, norm = CASES[name]
-    seed = 7000 + sorted(CASES).index(name)
+    return build_fused(CASES[name], 7000 + sorted(CASES).index(name))
+
+
+def build_fused(shape, seed, N=N):
+    """fused_case's recipe for a shape tuple laid out as CASES' values, on N > 7 bases."""
+    S, Sb, d, cov, ragged, T, K, smooth, norm = shape
     cs = make_case(N, 2, S, Sb, d, cov, seed=seed, ragged=ragged, tau=T)
     base = cs["base"]
     om = np.ones(N)
@@ -128,8 +132,13 @@ def schedule(request, capi_lib):
 
 
 def check_fused(vb, name, vec, Z):
-    base, h, opt, es, want = fused_case(name)
-    S, Sb, d, cov, ragged, T, K, smooth, norm = CASES[name]
+    check_fused_shape(vb, name, CASES[name], fused_case(name), vec, Z)
+
+
+def check_fused_shape(vb, name, shape, case, vec, Z):
+    """check_fused's bars on a build_fused case."""
+    base, h, opt, es, want = case
+    S, Sb, d, cov, ragged, T, K, smooth, norm = shape
     got = vb.host.unpack_stats(vec, K, S, d, cov)
     figs = {k: stat_err(got[k], want[k]) for k in ("N1", "M", "Nr", "Y", "SC")}
     figs["Nj"] = stat_err(got["Nj"], want["Nj"])
