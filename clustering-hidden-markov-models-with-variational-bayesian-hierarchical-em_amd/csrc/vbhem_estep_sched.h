@@ -43,3 +43,8 @@ const char *last_kernel(int pass);
 // which comes last; returns the workspace's bytes (0: bad arguments)
 extern "C" size_t vbhem_fused_workspace_layout(const vbhem_base_t *base, const vbhem_cluster_t *clus,
                                                int T, int R, long long *out);
+
+// (exported for the tests) fb_bwd4_kernel's persistent grid for K clusters of nbases bases on
+// the current device: out [3] = bases per quad (one wave's tile), waves per block, blocks per
+// cluster.  A wave takes every (blocks per cluster x waves per block)-th quad of its cluster.
+extern "C" int vbhem_bwd4_launch_plan(int K, int nbases, int *out);

@@ -433,6 +433,7 @@ int run_fb(const FbCtx &c, const Pass &p, double *Ebuf, long long e_ld, double *
     switch (kern) {
       case BwdKernel::kBwd4:
         label = "fb_bwd4_kernel"; targs = tf(bwd4_o32(ca));
+        if (switches().NO_BWD4_TRIM > 0) targs = bwd4_o32(ca) ? "true, false>" : "false, false>";
         e = launch_bwd4(ca, grid(bwd4_ppb(), bwd4_resident_blocks()), st, ev0, ev1);
         break;
       case BwdKernel::kBwd12:
@@ -743,4 +744,15 @@ extern "C" size_t vbhem_fused_workspace_layout(const vbhem_base_t *base, const v
   out[3] = at(w.gmask);
   out[4] = at(w.scratch);
   return bytes;
+}
+
+extern "C" int vbhem_bwd4_launch_plan(int K, int nbases, int *out) {
+  if (K < 1 || nbases < 1 || !out) return VBHEM_ERR_ARG;
+  const unsigned ppb = (unsigned)vbhem::bwd4_ppb();
+  const unsigned tiles = ((unsigned)nbases + ppb - 1) / ppb;
+  out[0] = vbhem::bwd4_ppb() / vbhem::bwd4_waves();
+  out[1] = vbhem::bwd4_waves();
+  out[2] = (int)vbhem::persistent_blocks(tiles, resident_blocks(vbhem::bwd4_resident_blocks()),
+                                        (unsigned)K);
+  return VBHEM_OK;
 }

@@ -43,6 +43,7 @@
 
 #include "vbhem_internal.h"
 #include "vbhem_mfma4.h"
+#include "vbhem_switches.h"
 
 #ifndef VBHEM_BWD4_WAVES
 #define VBHEM_BWD4_WAVES 4   // waves per SIMD
@@ -72,11 +73,29 @@ namespace {
 
 constexpr int kWaves = VBHEM_BWD4_WAVES;
 constexpr int kNWB = 16;   // waves per block: one block per CU, the 144 KB of tables once per CU
+// TRIM: the least lpi for which K3's clamp at -7.2e5 cannot act on an in-range V
+// (-7.2e5 + kVMax = -2e4, half of it left to V's slack over kVMax)
+constexpr double kLpiSafe = -1.0e4;
 using namespace m4;
 
 }  // namespace
 
-template <bool O32>
+// TRIM (round 9): a quad's work around its step loop cut down --
+//   * the tile loop unrolled by two over ping-pong input registers: the prefetched tile
+//     is used where it was loaded, no copy of its 9 doubles per quad
+//   * the head's tests as one unordered compare per value (|E|, |Ef| not below vlim: out
+//     of range, infinite or NaN) into one wave mask; the ordered range mask and the
+//     non-finite test, which tell a pair to recompute from one to answer with NaN, only
+//     for a quad where that mask has a lane (it has one whenever either of them has)
+//   * K3's clamp of lpi + V at -7.2e5 only where it can act: with every lpi of the
+//     cluster >= kLpiSafe, every A' entry finite and a quad that passed the range, the
+//     non-finite and (without ZS) the underflow tests, V is finite and above -kVMax - 8
+//     (|V| <= T (vlim + log S) (1 + 1e-6)^T), so lpi + V > -7.2e5 and fmax returns its
+//     first operand.  A quad with any failing lane takes the clamped K3 as a whole.
+// Without TRIM the kernel is the one of rounds 3-8 (VBHEM_NO_BWD4_TRIM=1).
+// (the tile loop's body is the kernel's own: behind a call with the arguments by reference the
+// step loop was selected and scheduled differently, 1.235 -> 1.259 ms per C4 launch)
+template <bool O32, bool TRIM = true>
 __global__ __launch_bounds__(64 * kNWB) __attribute__((amdgpu_waves_per_eu(kWaves)))
 void fb_bwd4_kernel(const SplitArgs p) {
   constexpr int S = 8;
@@ -132,6 +151,14 @@ void fb_bwd4_kernel(const SplitArgs p) {
     zsafe = am >= 0x1p-600;  // NaN: not safe
   }
   zsafe = __builtin_amdgcn_readfirstlane((int)zsafe) != 0;
+  // TRIM: K3's clamp is the identity for this cluster's in-range quads (above)
+  bool lps = false;
+  if constexpr (TRIM) {
+    bool ok = isfinite(AT[0][0]) && isfinite(AT[0][1]) && isfinite(AT[1][0]) && isfinite(AT[1][1]);
+#pragma unroll
+    for (int x = 0; x < S; ++x) ok = ok && lpi[x] >= kLpiSafe;  // NaN, -inf: not safe
+    lps = __ballot(!ok) == 0;
+  }
   // ds_bpermute sources of the log's column maxima (Q layout: column 4J + r)
   const int qsrc0 = (0 * 16 + 4 * b + r) << 2, qsrc1 = (1 * 16 + 4 * b + r) << 2;
   const unsigned long long pmask = 0x000F000F000F000Full << (4 * b);
@@ -187,12 +214,51 @@ void fb_bwd4_kernel(const SplitArgs p) {
     const int be = 4 * (r & 1) + c;
     in.pr = ld(p.prior, (off_t_)ic * SBk + (be < SBk ? be : SBk - 1));
   };
-  TileIn cur;
-  if (wave * NB + t0 < ntile) load_tile(wave * NB + t0, cur);
-  for (int tile = wave * NB + t0; tile < ntile; tile += tstride) {
+  // TRIM, O32 and F8: the tile's part of every load address as a uniform base, the lane's
+  // part, which no tile changes, from three registers set here: 1 VALU instruction per whole
+  // tile (the tile index made uniform) instead of 18.  A tile with bases past i_end (the
+  // last one) moves the lanes of those bases back to base i_end - 1, as load_tile's clamp
+  constexpr bool FASTLD = O32 && TRIM && F8;
+  unsigned cA = 0, cE = 0, cP = 0;  // byte offsets of a[0][0], e[0][0], pr in tile 0
+  if constexpr (FASTLD) {
+    cA = 8u * ((unsigned)(p.i_begin + b) * 64u + (unsigned)(c * 8 + r));
+    cE = 8u * ((unsigned)(j * S + r) * (unsigned)p.e_ld + (unsigned)(p.i_begin + b - p.i_buf0) * 8u + (unsigned)c);
+    cP = 8u * ((unsigned)(p.i_begin + b) * 8u + (unsigned)(4 * (r & 1) + c));
+  }
+  auto load_next = [&](int tile, TileIn &in) __attribute__((always_inline)) {
+    if constexpr (FASTLD) {
+      const int ts = __builtin_amdgcn_readfirstlane(tile);
+      unsigned oA = cA, oE = cE, oP = cP;
+      const int over = ts * 4 + 4 - (p.i_end - p.i_begin);  // bases of the tile past i_end
+      if (over > 0) {
+        const unsigned back = (unsigned)max(b - (3 - over), 0);
+        oA -= back * (64u * 8u);
+        oE -= back * (8u * 8u);
+        oP -= back * (8u * 8u);
+      }
+      const char *As = reinterpret_cast<const char *>(p.A) + (size_t)ts * (4 * 64 * 8);
+      const char *Es = reinterpret_cast<const char *>(p.E) + (size_t)ts * (4 * 8 * 8);
+      const char *Ps = reinterpret_cast<const char *>(p.prior) + (size_t)ts * (4 * 8 * 8);
+      const size_t erow4 = (size_t)p.e_ld * (4 * 8);  // four rows of E, bytes
+#pragma unroll
+      for (int j2 = 0; j2 < 2; ++j2)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)  // be = 4 jj + c: 4 rows of 8 doubles; bp = 4 j2 + r
+          in.a[j2][jj] = *reinterpret_cast<const double *>(As + oA + (jj * 256 + j2 * 32));
+#pragma unroll
+      for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+          in.e[i2][jj] = *reinterpret_cast<const double *>(Es + i2 * erow4 + oE + jj * 32);
+      in.pr = *reinterpret_cast<const double *>(Ps + oP);
+    } else {
+      load_tile(tile, in);
+    }
+  };
+  // one tile: the recursion on the inputs in cur, the next tile's loads into nxt
+  auto one_tile = [&](const int tile, const TileIn &cur, TileIn &nxt) __attribute__((always_inline)) {
     const int i = p.i_begin + tile * 4 + b;
-    TileIn nxt;
-    load_tile(min(tile + tstride, ntile - 1), nxt);  // (past the last tile: a repeat)
+    load_next(min(tile + tstride, ntile - 1), nxt);  // (past the last tile: a repeat)
     double Ef[2][2], V[2][2], AbT[2][2];
     // B operand of V = sv Ab^T + Ef, block (J', J): Ab[4J + c][4J' + r] (zero past SB)
 #pragma unroll
@@ -204,6 +270,7 @@ void fb_bwd4_kernel(const SplitArgs p) {
       }
     bool nf = false;
     uint64_t bigm = 0;  // the lanes failing the range check
+    uint64_t fail = 0;  // TRIM: the lanes with a value that is not inside the range
     // row sums of Ab (P layout: every lane row holds column 4J + c's sum), then
     // Ef = E + amax[sigma] rowsum(Ab)[beta] as one fma per element (the P layout's row
     // sigma = 4I + r)
@@ -218,13 +285,33 @@ void fb_bwd4_kernel(const SplitArgs p) {
         const double e = cur.e[i2][jj];
         V[i2][jj] = e;
         Ef[i2][jj] = fma(amr, rsj[jj], e);
-        bigm |= ge_mask(fabs(e), vlim);
-        bigm |= ge_mask(fabs(Ef[i2][jj]), vlim);
-        nf |= !isfinite(Ef[i2][jj]);
+        if constexpr (TRIM) {
+          // (not less than: out of range, infinite or NaN)
+          fail |= nlt_mask(fabs(e), vlim);
+          fail |= nlt_mask(fabs(Ef[i2][jj]), vlim);
+        } else {
+          bigm |= ge_mask(fabs(e), vlim);
+          bigm |= ge_mask(fabs(Ef[i2][jj]), vlim);
+          nf |= !isfinite(Ef[i2][jj]);
+        }
       }
     }
-    bigm |= gt_mask(rsj[0], 1.0 + 1e-6);
-    bigm |= gt_mask(rsj[1], 1.0 + 1e-6);
+    if constexpr (TRIM) fail |= gt_mask(rsj[0], 1.0 + 1e-6) | gt_mask(rsj[1], 1.0 + 1e-6);
+    // TRIM: the range and the non-finite masks only for a quad with a failing lane
+    if (!TRIM || fail != 0) {
+      if constexpr (TRIM) {
+#pragma unroll
+        for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj) {
+            bigm |= ge_mask(fabs(cur.e[i2][jj]), vlim);
+            bigm |= ge_mask(fabs(Ef[i2][jj]), vlim);
+            nf |= !isfinite(Ef[i2][jj]);
+          }
+      }
+      bigm |= gt_mask(rsj[0], 1.0 + 1e-6);
+      bigm |= gt_mask(rsj[1], 1.0 + 1e-6);
+    }
     int zmin = 0x7fffffff;
 
     // ---- K2: backward recursion, t = T-1 .. 1 ----
@@ -290,14 +377,18 @@ void fb_bwd4_kernel(const SplitArgs p) {
 
     // ---- K3: termination, L_elbo = sum_beta prior_beta log sum_sigma exp(lpi + E + L) ----
     // (the x1 reduction: m = the full column maximum of lo(s), M = m ln2/2048)
-    {
+    double y;
+    bool bad;
+    auto k3 = [&](auto clamp_tag) __attribute__((always_inline)) {
+      constexpr bool CLAMP = decltype(clamp_tag)::value;
       double W[2][2], s[2][2];
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
           // (a state of zero initial probability: lpi = -inf, kept in the integer range)
-          W[i2][jj] = fmax(lpi[4 * i2 + r] + V[i2][jj], -7.2e5);
+          const double wv = lpi[4 * i2 + r] + V[i2][jj];
+          W[i2][jj] = CLAMP ? fmax(wv, -7.2e5) : wv;
           s[i2][jj] = red_s(W[i2][jj]);
         }
       const unsigned w = colmax_rows(max(lo_u(s[0][0]), lo_u(s[1][0])), max(lo_u(s[0][1]), lo_u(s[1][1])));
@@ -323,8 +414,18 @@ void fb_bwd4_kernel(const SplitArgs p) {
       const double lse = lse1[0];
       const int be = 4 * (r & 1) + c;
       const double pr = be < SBk ? cur.pr : 0.0;
-      double y = r < 2 ? pr * lse : 0.0;
-      const bool bad = zmin < kZMinHi || !isfinite(y);
+      y = r < 2 ? pr * lse : 0.0;
+      bad = zmin < kZMinHi || !isfinite(y);
+    };
+    if constexpr (TRIM) {
+      bool plain = lps && fail == 0;  // (no lane in fail: none in bigm, none non-finite)
+      if constexpr (!ZS) plain = plain && __ballot(zmin < kZMinHi) == 0;
+      if (plain) k3(std::false_type{});
+      else k3(std::true_type{});
+    } else {
+      k3(std::true_type{});
+    }
+    {
       y += shfl_xor_d(y, 1);
       y += shfl_xor_d(y, 2);
       y += shfl_xor_d(y, 16);
@@ -343,7 +444,24 @@ void fb_bwd4_kernel(const SplitArgs p) {
         }
       }
     }
-    cur = nxt;
+  };
+  const int tile0 = wave * NB + t0;
+  if constexpr (TRIM) {
+    TileIn ta, tb;
+    if (tile0 < ntile) load_tile(tile0, ta);
+    for (int tile = tile0; tile < ntile; tile += tstride) {
+      one_tile(tile, ta, tb);
+      tile += tstride;
+      if (tile >= ntile) break;
+      one_tile(tile, tb, ta);
+    }
+  } else {
+    TileIn cur, nxt;
+    if (tile0 < ntile) load_tile(tile0, cur);
+    for (int tile = tile0; tile < ntile; tile += tstride) {
+      one_tile(tile, cur, nxt);
+      cur = nxt;
+    }
   }
   };
   if (SB == 8) {
@@ -372,7 +490,9 @@ bool bwd4_o32(const SplitArgs &a) {
 hipError_t launch_bwd4(const SplitArgs &a, unsigned grid, hipStream_t st, hipEvent_t t0,
                        hipEvent_t t1) {
   if (!bwd4_supported(a.S, a.SB) || !a.Atg) return hipErrorInvalidValue;
-  auto *fn = bwd4_o32(a) ? &fb_bwd4_kernel<true> : &fb_bwd4_kernel<false>;
+  const bool o32 = bwd4_o32(a);
+  auto *fn = o32 ? &fb_bwd4_kernel<true> : &fb_bwd4_kernel<false>;
+  if (switches().NO_BWD4_TRIM > 0) fn = o32 ? &fb_bwd4_kernel<true, false> : &fb_bwd4_kernel<false, false>;
   if (t0)  // timing events recorded by the dispatch itself (the bench's roofline)
     hipExtLaunchKernelGGL(fn, dim3(grid), dim3(64 * kNWB), 0, st, t0, t1, 0, a);
   else

@@ -47,6 +47,10 @@ __device__ __forceinline__ uint64_t ge_mask(double x, double lim) {
 __device__ __forceinline__ uint64_t gt_mask(double x, double lim) {
   return __builtin_amdgcn_fcmp(x, lim, 2);  // FCMP_OGT
 }
+// unordered or >=: "not less than" (a NaN counts, unlike ge_mask)
+__device__ __forceinline__ uint64_t nlt_mask(double x, double lim) {
+  return __builtin_amdgcn_fcmp(x, lim, 11);  // FCMP_UGE
+}
 __device__ __forceinline__ bool lane_in(uint64_t m) { return (m >> __lane_id()) & 1; }
 
 // s_waitcnt vmcnt(0) alone (expcnt 7, lgkmcnt 15 on gfx9), issued where the only vector

@@ -16,6 +16,7 @@
   X(NSLAB, -1, "tests: at most n statistics slabs (1 .. 8192)")                                \
   X(NO_BWD2, 0, "backward pass on fb_split_kernel's backward mode, not fb_bwd2_kernel")        \
   X(NO_BWD4, 0, "S = 8: fb_bwd2_kernel<8> instead of fb_bwd4_kernel")                          \
+  X(NO_BWD4_TRIM, 0, "S = 8: fb_bwd4_kernel with the tile copy and K3's clamp of every quad")  \
   X(NO_BWD12, 0, "S = 12: fb_bwd2_kernel<12> instead of fb_bwd12_kernel")                      \
   X(NO_LIST4, 0, "S = 8: fb_split_kernel's list mode instead of fb_list4_kernel")              \
   X(NO_LIST12, 0, "S = 12: fb_split_kernel's list mode instead of fb_list12_kernel")           \
